@@ -9,14 +9,20 @@ over RCCL and a broadcast of the winning x, when N > 1.  Weak scaling: every ran
 owns --batch restarts.
 
   python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--chunk C]
+                  [--dump-outputs DIR] [--full]
   python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...
 
-Prints ONE JSON line on rank 0 (contract in the task statement), with
-``roofline`` for the dominant kernel (per-launch HIP-event time on the plan's
-stream), ``host_path`` (the drop-in grape_fidelity_grad with host arrays, PCIe
-included) and ``single_eval`` (nbatch = 1, as Optim's loop calls the reference),
-``cpu_baseline`` (the C++ port, 1 thread) and ``cpu_baseline_allcores`` (the port
-over restarts on the job's CPU share), all on rank 0 at N = 1 only.
+A plain run sets up, warms up, times the K steps and prints ONE JSON line on rank 0
+(``metric``, ``value``, ``unit``, ``ms_per_step``, ...), with ``roofline`` for the dominant
+kernel (per-launch HIP-event time on the plan's stream, taken inside the timed steps).
+``--dump-outputs DIR`` then writes what the last timed step computed (DIR/<name>.npy).
+
+``--full`` adds the legs that take runs of their own: ``c4_strong`` (the 256-restart
+strong-scaling sweep), ``whole_matrix_path`` (sectors disabled), ``host_path`` (the
+drop-in grape_fidelity_grad with host arrays, PCIe included), ``single_eval``
+(nbatch = 1, as Optim's loop calls the reference), ``c4_points``, ``cpu_baseline``
+(the C++ port, 1 thread) and ``cpu_baseline_allcores`` (the port over restarts on the
+job's CPU share), the last six on rank 0 at N = 1 only; each has its own --no-* switch.
 """
 from __future__ import annotations
 
@@ -843,6 +849,34 @@ def c5_report(args, B, L, world, value, elapsed, ktimes, d, nt, nparam):
     return out
 
 
+DUMP_BUDGET = 48 << 20  # bytes of --dump-outputs in all (float64), below the 64 MB a dump may take
+
+
+def dump_rows(count, row_bytes):
+    """Rows of a `count`-row output that --dump-outputs writes: all of them when they fit DUMP_BUDGET,
+    else a fixed sample (seed 0, ascending) -- the same rows in every run with the same arguments."""
+    keep = max(1, DUMP_BUDGET // row_bytes)
+    if count <= keep:
+        return np.arange(count)
+    return np.sort(np.random.default_rng(0).choice(count, size=keep, replace=False))
+
+
+def dump_outputs(outdir, arrays):
+    """Write {name: array} (torch or numpy, one row per evaluation) as outdir/<name>.npy in float64,
+    every array cut to the same dump_rows."""
+    import torch
+    os.makedirs(outdir, exist_ok=True)
+    count = len(next(iter(arrays.values())))
+    row_bytes = sum(8 * (a[0].numel() if torch.is_tensor(a) else a[0].size) for a in arrays.values())
+    rows = dump_rows(count, row_bytes)
+    for name, a in arrays.items():
+        if torch.is_tensor(a):
+            a = a[torch.as_tensor(rows, device=a.device)].cpu().numpy()
+        else:
+            a = np.asarray(a)[rows]
+        np.save(os.path.join(outdir, name + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
+
+
 def c4opt(args):
     """SURVEY.md 8d C4 run as the optimiser the reference wraps (FidelityCalculations.jl:161-218):
     B restarts (x_main = 2pi*0.001*U, theta = 2pi*U, seed 1000 + r) advance together in a
@@ -876,6 +910,8 @@ def c4opt(args):
     calls = int(res2.f_calls.sum())
     F = 1.0 - cost.fidelity_terms(res2.minimizer)[0]
     cost.close()
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"x": res2.minimizer, "infidelity": F})
     out = {"metric": "GRAPE gradient-evals/sec inside batched L-BFGS (C4 sweep), Rydberg CZ d=9 N_t=512",
            "value": calls / elapsed, "unit": "gradient-evals/s", "n_gpus": 1, "steps": args.steps,
            "warmup": args.warmup, "ms_per_step": elapsed / args.steps * 1e3, "higher_is_better": True,
@@ -901,7 +937,7 @@ def arcz(args):
                                   "ne=1 (amplitude error); nbatch=1 per call"}}
     se = single_eval(fp, 1, x, seconds=3.0)
     out.update({"value": se["value"], "single_eval": se})
-    if not args.no_cpu_baseline:
+    if args.full and not args.no_cpu_baseline:
         try:
             from oracle.cref import cref
             if cref.available():
@@ -937,9 +973,11 @@ def c2_closure(args):
         plan.fidelity_grad(X[:chunk])
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        plan.fidelity_grad(X)
+        res = plan.fidelity_grad(X)
     elapsed = time.perf_counter() - t0
     value = args.steps * B / elapsed
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"F": res[0], "F_dx": res[1]})
     # the two halves on their own: serial closure tables (one core) and the device part
     t = time.perf_counter()
     H, U0 = TB.host_tables(fp, X[:8], 1)
@@ -963,7 +1001,7 @@ def c2_closure(args):
                       "restarts_per_gpu": B, "evals_per_chunk": min(B, chunk), "table_workers": workers},
            "closure_tables_serial_ms_per_eval": serial_ms,
            "device_ms_per_eval_tables_prebuilt": device_ms}
-    if not args.no_cpu_baseline:
+    if args.full and not args.no_cpu_baseline:
         cb = cpu_baseline(args.cpu_seconds)
         out["cpu_baseline"] = cb
         out["vs_cpu"] = value / cb["value"]
@@ -1112,14 +1150,22 @@ def main():
                     help="GRAPE_OPT_* flags of the timed plan (A/B runs; c2/c3/c5 device legs and c4opt)")
     ap.add_argument("--sync-rows", action="store_true",
                     help="c4opt: the synchronous optimiser loop (rows wait for each other every iteration)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the legs that take runs of their own: the CPU baselines, "
+                         "the host-array and nbatch = 1 paths, the C4 points, the whole-matrix comparison and the "
+                         "C4 strong-scaling sweep (each with its --no-* switch); off: the timed steps only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last one computed as DIR/<name>.npy (float64: F, F_dx "
+                         "and, with error sources, F_d2err, F_d2err_dx as the device path lays them out; rank 0's "
+                         "restarts); outputs above 48 MiB in all are cut to a fixed seeded sample of restarts")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baselines")
     ap.add_argument("--no-host-paths", action="store_true",
-                    help="skip the host-array (PCIe-inclusive) and nbatch = 1 legs")
+                    help="--full without the host-array (PCIe-inclusive), nbatch = 1 and C4-point legs")
     ap.add_argument("--cpu-seconds", type=float, default=15.0)
     ap.add_argument("--no-whole-matrix", action="store_true",
-                    help="skip the C2 whole-matrix comparison leg (PMC passes: one pipeline per run)")
+                    help="--full without the C2 whole-matrix comparison leg (PMC passes: one pipeline per run)")
     ap.add_argument("--no-c4-strong", action="store_true",
-                    help="skip the C4 strong-scaling leg (256 restarts over the ranks)")
+                    help="--full without the C4 strong-scaling leg (256 restarts over the ranks)")
     ap.add_argument("--c4-total", type=int, default=256, help="restarts of the C4 strong-scaling leg")
     ap.add_argument("--dist", action="store_true",
                     help="run the multi-rank path (RCCL process group, the sweep's all_gather + "
@@ -1142,6 +1188,8 @@ def main():
     if world > 1 and args.workload in ("c4opt", "c2-closure", "arcz"):
         print(f"bench.py: --workload {args.workload} is a single-GPU leg", file=sys.stderr)
         sys.exit(2)
+    if args.dump_outputs and (args.workload == "arcz" or args.dry_run):
+        ap.error("--dump-outputs: the arcz latency leg and --dry-run have no timed steps to dump")
 
     import torch
     import torch.distributed as dist
@@ -1230,6 +1278,11 @@ def main():
     elapsed = time.perf_counter() - t0
     plan.synchronize()  # resolves the per-kernel events, raises on a singular Pade denominator
     plan.set_profiling(False)
+    if args.dump_outputs and rank == 0:  # what the last timed step left in the caller's buffers
+        arrays = {"F": F, "F_dx": Fdx}
+        if ne:
+            arrays.update({"F_d2err": Fd2, "F_d2err_dx": Fd2dx})
+        dump_outputs(args.dump_outputs, arrays)
     if use_dist:
         t = torch.tensor([elapsed], dtype=torch.float64, device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -1261,7 +1314,7 @@ def main():
             out["build_defines"] = list(_capi.build_defines())
     plan.close()
 
-    if not (c3 or c5) and not args.no_c4_strong:
+    if args.full and not (c3 or c5) and not args.no_c4_strong:
         def make_step(f, c):
             p = GrapePlan(fp, nparam=nparam, device=local, max_batch=max(1, c))
             p.set_stream(stream.cuda_stream)
@@ -1273,10 +1326,10 @@ def main():
         strong = c4_strong(make_step, world, rank, use_dist, torch.cuda.synchronize, total=args.c4_total)
         if rank == 0:
             out["c4_strong"] = strong
-    if rank == 0 and world == 1 and not (c3 or c5) and sectors[0][0] < d and not args.no_whole_matrix:
+    if args.full and rank == 0 and world == 1 and not (c3 or c5) and sectors[0][0] < d and not args.no_whole_matrix:
         out["whole_matrix_path"] = whole_matrix_leg(fp, nparam, X, F, Fdx, min(count, chunk), stream, args)
     if rank == 0:
-        if world == 1 and not args.no_host_paths:
+        if args.full and world == 1 and not args.no_host_paths:
             # the drop-in path as the reference's callers use it (host arrays, SURVEY.md 8d's
             # metric definition): a 4 096-restart batch per call, and single evaluations
             Xh = inputs(0, min(4096, B))
@@ -1284,7 +1337,7 @@ def main():
             out["single_eval"] = single_eval(fp, nparam, Xh[0])
             if not (c3 or c5):
                 out["c4_points"] = c4_points(fp, nparam, inputs, dev)
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             if c5:
                 out["cpu_baseline"] = cpu_baseline_c5(args.cpu_seconds, fp, c5_inputs(0, 1)[0],
                                                       "C5 + 2 error sources" if c5err else "C5")

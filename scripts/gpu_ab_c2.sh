@@ -13,7 +13,7 @@ for v in "$@"; do
     faulted $O/ab_tests_${TAG}_$v.log && { echo FAULT; exit 99; }
     [ $rc -ne 0 ] && exit $rc
   fi
-  timeout -k 10 300 python bench.py --steps ${STEPS:-10} --warmup 2 --no-cpu-baseline --no-host-paths ${BENCH_ARGS:-} > $O/ab_${TAG}_$v.log 2>&1
+  timeout -k 10 300 python bench.py --full --steps ${STEPS:-10} --warmup 2 --no-cpu-baseline --no-host-paths ${BENCH_ARGS:-} > $O/ab_${TAG}_$v.log 2>&1
   rc=$?; faulted $O/ab_${TAG}_$v.log && { echo FAULT; exit 99; }
   [ $rc -ne 0 ] && { echo "bench $v rc=$rc"; tail -5 $O/ab_${TAG}_$v.log; exit $rc; }
   python3 -c "

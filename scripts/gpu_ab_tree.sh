@@ -7,7 +7,7 @@ cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
 ROOT=$PWD; O=$ROOT/gpurun_out; mkdir -p $O; TAG=$1; shift
 for v in "$@"; do
   if [ "$v" = cur ]; then d=$ROOT; else d=$ROOT/abvar/$v; fi
-  (cd $d && timeout -k 10 300 python bench.py --steps ${STEPS:-10} --warmup 2 --no-cpu-baseline --no-host-paths ${BENCH_ARGS:-} > $O/abt_${TAG}_$v.log 2>&1)
+  (cd $d && timeout -k 10 300 python bench.py --full --steps ${STEPS:-10} --warmup 2 --no-cpu-baseline --no-host-paths ${BENCH_ARGS:-} > $O/abt_${TAG}_$v.log 2>&1)
   rc=$?
   grep -qE "HSA_STATUS_ERROR|illegal memory access|Memory access fault|hipErrorLaunchFailure|core dumped" $O/abt_${TAG}_$v.log && { echo FAULT; exit 99; }
   [ $rc -ne 0 ] && { echo "bench $v rc=$rc"; tail -5 $O/abt_${TAG}_$v.log; exit $rc; }

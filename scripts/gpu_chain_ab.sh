@@ -13,7 +13,7 @@ cd /tmp && export TMPDIR=/tmp
 for mode in chain nochain; do
   [ $mode = nochain ] && export GRAPE_NO_CHAIN=1
   timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/prof_${mode}_$TAG" -o run -- \
-      python3 "$ROOT/bench.py" --steps 5 --warmup 1 --no-cpu-baseline --no-host-paths > "$OUT/prof_${mode}_$TAG.log" 2>&1
+      python3 "$ROOT/bench.py" --full --steps 5 --warmup 1 --no-cpu-baseline --no-host-paths > "$OUT/prof_${mode}_$TAG.log" 2>&1
   rc=$?; echo "$mode rc=$rc"; grep '^{' "$OUT/prof_${mode}_$TAG.log" | tail -1 | head -c 120; echo
   [ $rc -ne 0 ] && exit $rc
 done

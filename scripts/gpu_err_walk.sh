@@ -12,7 +12,7 @@ rc=$?; echo "tests rc=$rc"; grep -E "PASSED|FAILED|ERROR|passed|failed|imgwalk" 
 faulted "$OUT/tests_$TAG.log" && { echo FAULT; exit 99; }
 [ $rc -ne 0 ] && exit $rc
 if [ -n "${BENCH:-}" ]; then
-  timeout -k 10 300 python bench.py --workload c3 --steps 10 --warmup 2 --no-cpu-baseline --no-host-paths ${BENCH_ARGS:-} > "$OUT/c3_$TAG.log" 2>&1
+  timeout -k 10 300 python bench.py --full --workload c3 --steps 10 --warmup 2 --no-cpu-baseline --no-host-paths ${BENCH_ARGS:-} > "$OUT/c3_$TAG.log" 2>&1
   rc=$?; echo "c3 rc=$rc"; faulted "$OUT/c3_$TAG.log" && { echo FAULT; exit 99; }
   [ $rc -ne 0 ] && { tail -5 "$OUT/c3_$TAG.log"; exit $rc; }
   grep '^{' "$OUT/c3_$TAG.log" | tail -1 > "$OUT/c3_$TAG.json"
@@ -21,7 +21,7 @@ fi
 if [ -n "${PROF:-}" ]; then
   cd /tmp && export TMPDIR=/tmp
   timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/prof_$PROF" -o run -- \
-    python3 "$ROOT/bench.py" --workload c3 --steps 5 --warmup 1 --no-cpu-baseline --no-host-paths ${BENCH_ARGS:-} > "$OUT/rocprof_$PROF.log" 2>&1
+    python3 "$ROOT/bench.py" --full --workload c3 --steps 5 --warmup 1 --no-cpu-baseline --no-host-paths ${BENCH_ARGS:-} > "$OUT/rocprof_$PROF.log" 2>&1
   rc=$?; echo "rocprof rc=$rc"
   [ $rc -ne 0 ] && exit $rc
   cut -d, -f1-4 "$OUT/prof_$PROF/run_kernel_stats.csv" | head -16

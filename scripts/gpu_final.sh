@@ -18,7 +18,7 @@ fi
 timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" > $OUT/${TAG}_smoke.log 2>&1
 rc=$?; echo "smoke rc=$rc"; tail -2 $OUT/${TAG}_smoke.log; [ $rc -ne 0 ] && exit $rc
 if [ -z "${SKIP_BENCH:-}" ]; then
-  timeout -k 10 600 python bench.py > $OUT/${TAG}_bench.log 2>&1
+  timeout -k 10 600 python bench.py --full > $OUT/${TAG}_bench.log 2>&1
   rc=$?; echo "bench rc=$rc"; faulted $OUT/${TAG}_bench.log && { echo FAULT; exit 99; }; [ $rc -ne 0 ] && exit $rc
   grep '^{' $OUT/${TAG}_bench.log | tail -1 | cut -c1-300
 fi

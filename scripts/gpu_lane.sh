@@ -13,9 +13,9 @@ timeout -k 10 900 python -u -m pytest tests/ -x -q -m gpu --timeout 120 --timeou
 rc=$?; echo "gpu suite rc=$rc"; tail -3 $OUT/pytest_gpu_$TAG.log
 if faulted $OUT/pytest_gpu_$TAG.log; then echo FAULT; exit 99; fi
 [ $rc -ne 0 ] && exit $rc
-timeout -k 10 300 python bench.py --steps 10 --warmup 2 --no-cpu-baseline --no-host-paths > $OUT/bench_lane_$TAG.log 2>&1
+timeout -k 10 300 python bench.py --full --steps 10 --warmup 2 --no-cpu-baseline --no-host-paths > $OUT/bench_lane_$TAG.log 2>&1
 rc=$?; echo "bench lane rc=$rc"; tail -c 1500 $OUT/bench_lane_$TAG.log | head -c 700; echo
 [ $rc -ne 0 ] && exit $rc
-GRAPE_NO_LANE=1 timeout -k 10 300 python bench.py --steps 10 --warmup 2 --no-cpu-baseline --no-host-paths > $OUT/bench_rowgroup_$TAG.log 2>&1
+GRAPE_NO_LANE=1 timeout -k 10 300 python bench.py --full --steps 10 --warmup 2 --no-cpu-baseline --no-host-paths > $OUT/bench_rowgroup_$TAG.log 2>&1
 rc=$?; echo "bench rowgroup rc=$rc"; tail -c 1500 $OUT/bench_rowgroup_$TAG.log | head -c 700; echo
 exit $rc

@@ -15,7 +15,7 @@ if faulted $OUT/pytest_gpu_$TAG.log; then echo FAULT; exit 99; fi
 [ $rc -ne 0 ] && exit $rc
 for mode in lane row; do
   if [ $mode = row ]; then export GRAPE_NO_LANE=1; fi
-  timeout -k 10 300 python bench.py --workload c3 --steps 10 --warmup 2 --no-cpu-baseline --no-host-paths > $OUT/bench_c3_${mode}_$TAG.log 2>&1
+  timeout -k 10 300 python bench.py --full --workload c3 --steps 10 --warmup 2 --no-cpu-baseline --no-host-paths > $OUT/bench_c3_${mode}_$TAG.log 2>&1
   rc=$?; echo "c3 $mode rc=$rc"; grep '^{' $OUT/bench_c3_${mode}_$TAG.log | tail -1 | head -c 300; echo
   [ $rc -ne 0 ] && exit $rc
 done

@@ -11,7 +11,7 @@ if [ -z "${NO_TESTS:-}" ]; then
   [ $rc -ne 0 ] && exit $rc
 fi
 bash scripts/gpu_single_prof.sh $TAG || exit $?
-timeout -k 10 400 python bench.py --steps 10 --warmup 2 --no-cpu-baseline > "$OUT/bench_$TAG.log" 2>&1
+timeout -k 10 400 python bench.py --full --steps 10 --warmup 2 --no-cpu-baseline > "$OUT/bench_$TAG.log" 2>&1
 rc=$?; echo "bench rc=$rc"; faulted "$OUT/bench_$TAG.log" && { echo FAULT; exit 99; }
 [ $rc -ne 0 ] && { tail -5 "$OUT/bench_$TAG.log"; exit $rc; }
 python3 -c "

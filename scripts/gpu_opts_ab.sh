@@ -8,7 +8,7 @@ faulted() { grep -qE "HSA_STATUS_ERROR|illegal memory access|Memory access fault
 i=0
 for v in "$@"; do
   i=$((i+1))
-  timeout -k 10 300 python bench.py --workload $WL --steps ${STEPS:-10} --warmup 2 --no-cpu-baseline --no-host-paths \
+  timeout -k 10 300 python bench.py --full --workload $WL --steps ${STEPS:-10} --warmup 2 --no-cpu-baseline --no-host-paths \
       --no-whole-matrix --plan-options $v ${BENCH_ARGS:-} > $O/opts_${TAG}_${i}_$v.log 2>&1
   rc=$?; faulted $O/opts_${TAG}_${i}_$v.log && { echo FAULT; exit 99; }
   [ $rc -ne 0 ] && { echo "bench $v rc=$rc"; tail -5 $O/opts_${TAG}_${i}_$v.log; exit $rc; }

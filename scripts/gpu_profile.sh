@@ -10,13 +10,13 @@ ARGS="--steps 10 --warmup 2 --no-cpu-baseline --no-host-paths --no-whole-matrix 
 faulted() { grep -qE "HSA_STATUS_ERROR|illegal memory access|Memory access fault|core dumped" "$1"; }
 cd /tmp && export TMPDIR=/tmp
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/${TAG}_stats -o run -- \
-    python3 $ROOT/bench.py $ARGS > $OUT/${TAG}_stats.log 2>&1
+    python3 $ROOT/bench.py --full $ARGS > $OUT/${TAG}_stats.log 2>&1
 rc=$?; echo "stats rc=$rc"; faulted $OUT/${TAG}_stats.log && { echo FAULT; exit 99; }; [ $rc -ne 0 ] && exit $rc
 i=0
 for ctr in FETCH_SIZE WRITE_SIZE; do
   i=$((i+1))
   timeout -k 10 300 rocprofv3 --pmc $ctr --kernel-trace --output-format csv -d $OUT/${TAG}_pmc$i -o run -- \
-      python3 $ROOT/bench.py $ARGS > $OUT/${TAG}_pmc$i.log 2>&1
+      python3 $ROOT/bench.py --full $ARGS > $OUT/${TAG}_pmc$i.log 2>&1
   rc=$?; echo "pmc $ctr rc=$rc"; faulted $OUT/${TAG}_pmc$i.log && { echo FAULT; exit 99; }; [ $rc -ne 0 ] && exit $rc
 done
 python3 $ROOT/scripts/pmc_summary.py $OUT/${TAG}_pmc1 $OUT/${TAG}_pmc2 --batch ${BATCH:-1024} --json $OUT/${TAG}_pmc.json > $OUT/${TAG}_pmc.txt

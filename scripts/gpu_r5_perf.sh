@@ -10,7 +10,7 @@ TAG=${1:-r5p}
 faulted() { grep -qE "HSA_STATUS_ERROR|illegal memory access|Memory access fault|hipErrorLaunchFailure|core dumped" "$1"; }
 run() {  # name, timeout, args...
   local name=$1 lim=$2; shift 2
-  timeout -k 10 $lim python -u bench.py "$@" > $OUT/${TAG}_$name.log 2>&1
+  timeout -k 10 $lim python -u bench.py --full "$@" > $OUT/${TAG}_$name.log 2>&1
   local rc=$?; echo "$name rc=$rc"; faulted $OUT/${TAG}_$name.log && { echo FAULT; exit 99; }
   [ $rc -ne 0 ] && { tail -5 $OUT/${TAG}_$name.log; exit $rc; }
   grep '^{' $OUT/${TAG}_$name.log | tail -1 | python3 -c "import sys,json; d=json.load(sys.stdin); print('  value', d['value'], 'ms/step', d['ms_per_step'], {k: round(v, 4) for k, v in d.get('kernels_ms_per_pass', d.get('kernels_ms_per_step', {})).items()})"

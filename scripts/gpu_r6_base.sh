@@ -7,7 +7,7 @@ O=gpurun_out; mkdir -p $O; TAG=${1:-r6base}
 faulted() { grep -qE "HSA_STATUS_ERROR|illegal memory access|Memory access fault|hipErrorLaunchFailure|core dumped" "$1"; }
 run() {  # name, limit, args...
   local n=$1 t=$2; shift 2
-  timeout -k 10 $t python bench.py "$@" > $O/${TAG}_$n.log 2>&1
+  timeout -k 10 $t python bench.py --full "$@" > $O/${TAG}_$n.log 2>&1
   local rc=$?; echo "$n rc=$rc"; faulted $O/${TAG}_$n.log && { echo FAULT; exit 99; }
   [ $rc -ne 0 ] && { tail -5 $O/${TAG}_$n.log; exit $rc; }
   grep '^{' $O/${TAG}_$n.log | tail -1 | cut -c1-400

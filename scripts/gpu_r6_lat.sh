@@ -14,7 +14,7 @@ if [ -n "${TESTS:-}" ]; then
 fi
 run() {  # variant leg limit args...
   local v=$1 n=$2 t=$3; shift 3
-  timeout -k 10 $t python bench.py "$@" > $O/${TAG}_${v}_$n.log 2>&1
+  timeout -k 10 $t python bench.py --full "$@" > $O/${TAG}_${v}_$n.log 2>&1
   local rc=$?; faulted $O/${TAG}_${v}_$n.log && { echo FAULT; exit 99; }
   [ $rc -ne 0 ] && { echo "$v $n rc=$rc"; tail -5 $O/${TAG}_${v}_$n.log; exit $rc; }
   python3 -c "

@@ -22,14 +22,14 @@ rc=$?; echo "smoke rc=$rc"; tail -3 "$OUT/smoke_$TAG.log"
 if faulted "$OUT/smoke_$TAG.log"; then echo "GPU FAULT in smoke"; exit 99; fi
 if [ $rc -ne 0 ]; then exit $rc; fi
 
-timeout -k 10 400 python bench.py --steps "$STEPS" --warmup 3 > "$OUT/bench_$TAG.log" 2>&1
+timeout -k 10 400 python bench.py --full --steps "$STEPS" --warmup 3 > "$OUT/bench_$TAG.log" 2>&1
 rc=$?; echo "bench rc=$rc"; tail -3 "$OUT/bench_$TAG.log"
 if faulted "$OUT/bench_$TAG.log"; then echo "GPU FAULT in bench"; exit 99; fi
 [ $rc -ne 0 ] && exit $rc
 
 cd /tmp && export TMPDIR=/tmp
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/prof_$TAG" -o run -- \
-    python3 "$ROOT/bench.py" --steps 10 --warmup 2 --no-cpu-baseline --no-host-paths > "$OUT/rocprof_$TAG.log" 2>&1
+    python3 "$ROOT/bench.py" --full --steps 10 --warmup 2 --no-cpu-baseline --no-host-paths > "$OUT/rocprof_$TAG.log" 2>&1
 rc=$?; echo "rocprof rc=$rc"; tail -3 "$OUT/rocprof_$TAG.log"
 find "$OUT/prof_$TAG" -name "*stats*" | head
 exit $rc

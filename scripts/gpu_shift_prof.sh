@@ -15,7 +15,7 @@ for v in base noshift base; do
   n=$((n+1))
   if [ "$v" = base ]; then unset GRAPE_LIB; else export GRAPE_LIB=$ROOT/abvar/libgrape_$v.so; fi
   timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$O/shiftp_${n}_$v" -o run -- \
-      python3 "$ROOT/bench.py" --steps 10 --warmup 2 --no-cpu-baseline --no-host-paths > "$O/shiftp_${n}_$v.log" 2>&1
+      python3 "$ROOT/bench.py" --full --steps 10 --warmup 2 --no-cpu-baseline --no-host-paths > "$O/shiftp_${n}_$v.log" 2>&1
   rc=$?; faulted "$O/shiftp_${n}_$v.log" && { echo FAULT; exit 99; }
   [ $rc -ne 0 ] && { echo "rocprof $v rc=$rc"; exit $rc; }
   f=$(find "$O/shiftp_${n}_$v" -name "*kernel_stats.csv" | head -1)

@@ -6,7 +6,7 @@ cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
 TAG=${1:-wl}; OUT=gpurun_out/workloads_$TAG; mkdir -p $OUT
 faulted() { grep -qE "HSA_STATUS_ERROR|illegal memory access|Memory access fault|hipErrorLaunchFailure|core dumped" "$1"; }
 for w in c3 c5 c5err c4opt c2-closure; do
-  timeout -k 10 400 python bench.py --workload $w --steps 10 --warmup 2 --no-cpu-baseline --no-host-paths > $OUT/$w.log 2>&1
+  timeout -k 10 400 python bench.py --full --workload $w --steps 10 --warmup 2 --no-cpu-baseline --no-host-paths > $OUT/$w.log 2>&1
   rc=$?; echo "$w rc=$rc"
   if faulted $OUT/$w.log; then echo FAULT; exit 99; fi
   [ $rc -ne 0 ] && { tail -5 $OUT/$w.log; exit $rc; }
