@@ -35,7 +35,7 @@
 extern "C" {
 #endif
 
-#define GRAPE_ABI_VERSION 11
+#define GRAPE_ABI_VERSION 12
 
 typedef enum grape_status {
     GRAPE_OK = 0,
@@ -52,8 +52,10 @@ typedef enum grape_status {
 /* Largest dimension served by the dense (MFMA) engine, used for
  * GRAPE_MAX_SMALL_DIM < ndim <= GRAPE_MAX_DENSE_DIM (zero-padded to 64).  It
  * requires a Hermitian H0 operator basis (Hermitian operators, real
- * coefficients) and H0 / error terms independent of x_add; error sources are
- * served (Hermitian error operators). */
+ * coefficients); error sources are served (Hermitian error operators).  Plans
+ * created with GRAPE_OPT_GENERAL_H0 (ABI 12) serve any H0 and any error
+ * generator at these dimensions: the general path over the dense engine's
+ * pivoted exponential (grape_dense.hpp gj_solve_pivot). */
 #define GRAPE_MAX_DENSE_DIM 64
 
 /*
@@ -136,7 +138,8 @@ typedef struct grape_desc {
  * reference and passes the tables to grape_fidelity_grad_tables.  ops / terms
  * may then be NULL (n_ops = 0); ndim <= GRAPE_MAX_DENSE_DIM (above GRAPE_MAX_SMALL_DIM the
  * tables go through the general path below with the dense engine's exponential, which needs
- * Hermitian tabulated generators -- the Python host checks).  The closures may read x_add:
+ * Hermitian tabulated generators -- the Python host checks -- unless the plan was created with
+ * GRAPE_OPT_GENERAL_H0, which selects the pivoted exponential: any tables, ABI 12).  The closures may read x_add:
  * every x_add call site of the reference is tabulated.
  */
 #define GRAPE_DESC_HOST_TABLES 1
@@ -161,8 +164,14 @@ typedef struct grape_desc {
  * and the fidelity path runs from the materialised unitary derivatives, one evaluation at a
  * time (FidelityCalculations.jl:19-119).  Selected automatically for an operator-basis H0
  * that is not Hermitian; host-table plans (closures) set it when the host sees a
- * non-Hermitian H0 table.  Operator bases: ndim <= GRAPE_MAX_SMALL_DIM; host-table plans above
- * GRAPE_MAX_SMALL_DIM always take this path (Hermitian tables only).
+ * non-Hermitian H0 table.  Above GRAPE_MAX_SMALL_DIM nothing is selected automatically: a
+ * default plan refuses a non-Hermitian operator-basis H0 or error source (GRAPE_ERR_UNSUPPORTED),
+ * and host-table plans, which always take this path there, need Hermitian tables.  Setting the
+ * option at GRAPE_MAX_SMALL_DIM < ndim <= GRAPE_MAX_DENSE_DIM (ABI 12) lifts both: the Hermitian
+ * checks of H0 and of every error source are skipped, and every exponential (operator basis and
+ * host tables alike) runs the dense engine's pivoted kernel, valid for any generator.  Such plans
+ * serve grape_fidelity_grad*, grape_unitary_derivs*, the interaction operators and the
+ * expectation values; not the time slices.  On a Hermitian problem the option is a cross-path.
  */
 #define GRAPE_OPT_GENERAL_H0 64
 /* Calls of at most 4096 evaluations on a plan with two sector classes run the second class on an
@@ -509,8 +518,18 @@ int grape_symmetry_basis(const grape_desc *desc, double *V, int *block);
  * dense engine's solve needs a skew-Hermitian A, see grape_dense.hpp) on `device`, with the reference's algorithm (Julia
  * LinearAlgebra.exp!: Pade degree by 1-norm, gesv, squaring).  Host buffers.
  * stats (optional, 5 ints) receives how many matrices used Pade m=3,5,7,9,13.
+ * For a general A above GRAPE_MAX_SMALL_DIM use grape_expm_batch_general.
  */
 int grape_expm_batch(int device, int ndim, int n, const double *A, double *E, int *stats);
+
+/*
+ * ABI 12: the same for ANY A (same layout, same stats).  GRAPE_MAX_SMALL_DIM < ndim <=
+ * GRAPE_MAX_DENSE_DIM runs the dense engine's pivoted kernel (partial pivoting in the Pade
+ * solve, Julia's scaling s = ceil(log2(|A|_1 / 5.4))); smaller ndim runs the small engine's
+ * exponential as grape_expm_batch does.  A is not balanced on the device: m (stats) and s follow
+ * the 1-norm of A as given.
+ */
+int grape_expm_batch_general(int device, int ndim, int n, const double *A, double *E, int *stats);
 
 #ifdef __cplusplus
 }

@@ -13,6 +13,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("GRAPE_LIB") or os.path.join(HERE, "libgrape.so")
 
 GRAPE_OK = 0
+ERR_UNSUPPORTED = -2
 STATUS_NAMES = {-1: "GRAPE_ERR_INVALID", -2: "GRAPE_ERR_UNSUPPORTED", -3: "GRAPE_ERR_ALLOC",
                 -4: "GRAPE_ERR_HIP", -5: "GRAPE_ERR_SINGULAR", -6: "GRAPE_ERR_NO_DEVICE"}
 
@@ -27,11 +28,12 @@ EXPORTED = ["grape_abi_version", "grape_build_id", "grape_last_error", "grape_in
             "grape_expectation_values_tables", "grape_plan_sectors", "grape_lbfgs_ls_init", "grape_lbfgs_ls_begin",
             "grape_lbfgs_ls_end", "grape_lbfgs_step", "grape_robust_cost", "grape_slice_forward",
             "grape_slice_gradient", "grape_symmetry_basis", "grape_plan_sector_info", "grape_lbfgs_async_advance",
-            "grape_slice_forward_device", "grape_slice_gradient_device", "grape_plan_gauge_info", "grape_plan_eval1"]
+            "grape_slice_forward_device", "grape_slice_gradient_device", "grape_plan_gauge_info", "grape_plan_eval1",
+            "grape_expm_batch_general"]
 KERNEL_NAMES = ["k_expm", "k_expm_high", "k_scan", "k_grad/k_err_local", "k_reduce_add", "k_err_scan", "k_err_grad",
                 "k_expm_grad", "k_grad_high", "k_dexp", "k_dscan", "k_dcarry", "k_dmc", "k_dgrad",
                 "k_walk_fwd", "k_walk_grad", "k_eval1"]
-ABI_VERSION = 11  # GRAPE_ABI_VERSION in include/grape.h
+ABI_VERSION = 12  # GRAPE_ABI_VERSION in include/grape.h
 
 
 class GrapeError(RuntimeError):
@@ -96,6 +98,8 @@ def lib():
         L.grape_expm_batch.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int, dp, dp,
                                        ctypes.POINTER(ctypes.c_int)]
         L.grape_expm_batch.restype = ctypes.c_int
+        L.grape_expm_batch_general.argtypes = L.grape_expm_batch.argtypes
+        L.grape_expm_batch_general.restype = ctypes.c_int
         L.grape_interaction_error_operators.argtypes = [vp, dp, dp]
         L.grape_interaction_error_operators.restype = ctypes.c_int
         L.grape_interaction_error_operators_device.argtypes = [vp, dp, vp]

@@ -142,6 +142,36 @@ __global__ __launch_bounds__(NTHREADS, 1) void k_dexp_raw(const double *Ain, dou
     note_m(mstats, m);
 }
 
+// k_dexp / k_dexp_raw for a general generator: wg_expm<true> (pivoted Pade solve, grape_dense.hpp)
+__global__ __launch_bounds__(NTHREADS, 1) void k_dexp_piv(DenseProblem DP, DenseBatch B) {
+    extern __shared__ double lds[];
+    const Lane ln = make_lane();
+    const grape::DevProblem &P = DP.P;
+    const long item = blockIdx.x;  // (b, k, v), v fastest; E[b][k][v]
+    const int v = (int)(item % P.nv), k = (int)((item / P.nv) % P.Nt), b = (int)(item / ((long)P.nv * P.Nt));
+    HM X;
+    const double *xb = B.x + (size_t)b * P.nx;
+    bool singular = false;
+    const grape::VSpec vs = P.vs[v];
+    const int m = wg_expm<true>([&](HM &A) { build_variant(DP, xb, k, vs, A, ln); }, X, lds, ln, singular);
+    img_store(B.E + (size_t)item * IMG, X, ln);
+    if (singular) atomicOr(B.status, 1);
+    note_m(B.mstats, m);
+}
+
+__global__ __launch_bounds__(NTHREADS, 1) void k_dexp_raw_piv(const double *Ain, double *Eout, int *status,
+                                                               int *mstats) {
+    extern __shared__ double lds[];
+    const Lane ln = make_lane();
+    HM X;
+    const double *src = Ain + (size_t)blockIdx.x * IMG;
+    bool singular = false;
+    const int m = wg_expm<true>([&](HM &A) { img_load(src, A, ln); }, X, lds, ln, singular);
+    img_store(Eout + (size_t)blockIdx.x * IMG, X, ln);
+    if (singular) atomicOr(status, 1);
+    note_m(mstats, m);
+}
+
 // chunk-local prefix products Q_k = E_k Q_{k-1}
 __global__ __launch_bounds__(NTHREADS, 1) void k_dscan(DenseProblem DP, DenseBatch B) {
     extern __shared__ double lds[];
@@ -732,7 +762,8 @@ hipError_t set_lds_limits() {
                         reinterpret_cast<const void *>(&k_dmc),       reinterpret_cast<const void *>(&k_dgrad),
                         reinterpret_cast<const void *>(&k_dlocal),    reinterpret_cast<const void *>(&k_dwsum),
                         reinterpret_cast<const void *>(&k_derr_scan), reinterpret_cast<const void *>(&k_dmce),
-                        reinterpret_cast<const void *>(&k_derr_grad)};
+                        reinterpret_cast<const void *>(&k_derr_grad), reinterpret_cast<const void *>(&k_dexp_piv),
+                        reinterpret_cast<const void *>(&k_dexp_raw_piv)};
     for (const void *f : fs) {
         hipError_t e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLds);
         if (e != hipSuccess) return e;
@@ -770,9 +801,11 @@ __global__ __launch_bounds__(256) void k_img_rows(const double *img, grape::cd *
     }
 }
 
-hipError_t launch_variant_table(const DenseProblem &P, const DenseBatch &B, grape::cd *rows, hipStream_t st) {
+hipError_t launch_variant_table(const DenseProblem &P, const DenseBatch &B, grape::cd *rows, hipStream_t st,
+                                bool pivot) {
     const unsigned n = (unsigned)((long)B.nb * P.P.Nt * P.P.nv);
-    hipLaunchKernelGGL(k_dexp, dim3(n), dim3(NTHREADS), kLds, st, P, B);
+    if (pivot) hipLaunchKernelGGL(k_dexp_piv, dim3(n), dim3(NTHREADS), kLds, st, P, B);
+    else hipLaunchKernelGGL(k_dexp, dim3(n), dim3(NTHREADS), kLds, st, P, B);
     hipLaunchKernelGGL(k_img_rows, dim3(n), dim3(256), 0, st, B.E, rows, P.P.D);
     return hipGetLastError();
 }
@@ -877,17 +910,20 @@ __global__ __launch_bounds__(256) void k_tab_images(const grape::cd *H, double *
 }
 
 hipError_t launch_table_variants(const grape::cd *H, int D, int n, double dt, double *Aimg, double *Eimg,
-                                 grape::cd *rows, int *status, hipStream_t st) {
+                                 grape::cd *rows, int *status, hipStream_t st, bool pivot) {
     if (n <= 0) return hipSuccess;
     hipLaunchKernelGGL(k_tab_images, dim3((unsigned)n), dim3(256), 0, st, H, Aimg, D, dt);
-    hipLaunchKernelGGL(k_dexp_raw, dim3((unsigned)n), dim3(NTHREADS), kLds, st, Aimg, Eimg, status, nullptr);
+    if (pivot)
+        hipLaunchKernelGGL(k_dexp_raw_piv, dim3((unsigned)n), dim3(NTHREADS), kLds, st, Aimg, Eimg, status, nullptr);
+    else hipLaunchKernelGGL(k_dexp_raw, dim3((unsigned)n), dim3(NTHREADS), kLds, st, Aimg, Eimg, status, nullptr);
     hipLaunchKernelGGL(k_img_rows, dim3((unsigned)n), dim3(256), 0, st, Eimg, rows, D);
     return hipGetLastError();
 }
 
-hipError_t launch_expm_raw(const double *A, double *E, int n, int *status, int *mstats, hipStream_t st) {
+hipError_t launch_expm_raw(const double *A, double *E, int n, int *status, int *mstats, hipStream_t st, bool pivot) {
     if (n <= 0) return hipSuccess;
-    hipLaunchKernelGGL(k_dexp_raw, dim3((unsigned)n), dim3(NTHREADS), kLds, st, A, E, status, mstats);
+    if (pivot) hipLaunchKernelGGL(k_dexp_raw_piv, dim3((unsigned)n), dim3(NTHREADS), kLds, st, A, E, status, mstats);
+    else hipLaunchKernelGGL(k_dexp_raw, dim3((unsigned)n), dim3(NTHREADS), kLds, st, A, E, status, mstats);
     return hipGetLastError();
 }
 

@@ -703,6 +703,185 @@ __device__ __forceinline__ void gj_solve(HM &Q, HM &Pm, double *lds, const Lane 
 }
 
 // ---------------------------------------------------------------------------
+// Solve Q X = Pm for a GENERAL Q (X returned in Pm): blocked Gauss-Jordan with partial (row)
+// pivoting inside each 64 x 16 panel, the interchanges implicit (rows stay where they are; the
+// permutation is applied once, when X is read back).  Q and Pm stay in registers as in gj_solve.
+// Block step kb (columns 16 kb .. 16 kb + 15), buffers overlaying the two free matrix regions:
+//   a. waves (kb, *) publish their Q tiles: the 64 x 16 panel (PV_PAN);
+//   b. wave 0 factors the panel, lane = row, the row's 16 entries in registers: 16 steps of
+//      in-place Gauss-Jordan, the pivot of step j the arg-max of |re| + |im| over the rows no block
+//      step has used yet.  With pi_j the pivot rows, D = Q[pi, panel] and L = Q[:, panel], the panel
+//      ends as G: rows pi hold D^-1, every other row r holds -(L D^-1)[r] (PV_G; pi in PV_PJ / PV_PERM);
+//   c. every wave publishes its entries of the 16 pivot rows of [Q | Pm] (PV_PRQ, PV_PRP);
+//   d. rank-16 update on MFMA: row r of [Q | Pm] becomes [r not in pi] row r + G[r] . rows pi, i.e.
+//      D^-1 (rows pi) for a pivot row and row r - (L D^-1)[r] (rows pi) for any other.
+// After four block steps row pi_k of Q is the unit vector e_k, so X[k] = Pm[pi_k].
+// Partial pivoting over the whole column needs nothing beyond the panel: when panel kb is factored,
+// the earlier block steps have already been applied to it (step d), so step j's arg-max runs over
+// the fully updated column 16 kb + j, exactly as in the unblocked elimination.
+// NaN / Inf: a NaN magnitude counts as 0 in the arg-max, whose (value, row) order is total, and at
+// every step at least one row is unused (64 rows, 64 steps) and compares above the used ones (-1):
+// the pivot row is always a valid unused row, whatever the data; NaNs only propagate into X.
+// ---------------------------------------------------------------------------
+constexpr int PV_PAN = 0;                      // panel: 2 planes x 64 x 16 (sidx16)
+constexpr int PV_G = PV_PAN + 2 * 4 * SMALL;   // G: 2 planes x 64 x 16 (sidx16: A fragments)
+constexpr int PV_PRQ = PV_G + 2 * 4 * SMALL;   // pivot rows of Q: 2 planes x 16 x 64 (pv_pridx)
+constexpr int PV_PRP = PV_PRQ + 2 * 4 * SMALL; // pivot rows of Pm
+static_assert(PV_PRP + 2 * 4 * SMALL <= 2 * PLANE, "pivot buffers must fit matrix region 0");
+constexpr int PV_PJ = 0;     // ints at the start of region 1: [64] row -> j of this block step, or -1
+constexpr int PV_PERM = 64;  // [64] column k -> its pivot row
+
+// 16 x 64 buffer read as B fragments (rows 4s + g, g = l >> 4): the rotation by 16 (j & 3) puts the
+// four rows of one fragment into four distinct 16-double windows of the 64 banks
+__device__ __forceinline__ int pv_pridx(int j, int col) { return j * N + ((col + 16 * (j & 3)) & (N - 1)); }
+
+// one wave, lane = row: in-place pivoted Gauss-Jordan of the panel (step b above)
+__device__ __forceinline__ void pv_panel(double *buf, int *ibuf, int kb, int l, bool &used, bool &singular) {
+    const double *pr_ = buf + PV_PAN, *pi_ = pr_ + 4 * SMALL;
+    double ar[16], ai[16];
+#pragma unroll
+    for (int c = 0; c < 16; ++c) {
+        ar[c] = pr_[sidx16(l, c)];
+        ai[c] = pi_[sidx16(l, c)];
+    }
+    int myj = -1;
+#pragma unroll
+    for (int j = 0; j < 16; ++j) {
+        double mag = fabs(ar[j]) + fabs(ai[j]);
+        if (!(mag == mag)) mag = 0.0;  // NaN: a total order for the arg-max
+        if (used) mag = -1.0;
+        int p = l;
+#pragma unroll
+        for (int o = 32; o >= 1; o >>= 1) {  // (larger value, then lower row) wins: the same in every lane
+            const double om = __shfl_xor(mag, o, 64);
+            const int op = __shfl_xor(p, o, 64);
+            const bool take = om > mag || (om == mag && op < p);
+            mag = take ? om : mag;
+            p = take ? op : p;
+        }
+        p = __builtin_amdgcn_readfirstlane(p) & 63;
+        const double qr = __shfl(ar[j], p, 64), qi = __shfl(ai[j], p, 64);
+        if (qr == 0.0 && qi == 0.0) singular = true;
+        const cd inv = crecip_smith(grape::cmake(qr, qi));
+        const bool isp = l == p;
+        const double mr = ar[j], mi = ai[j];  // my multiplier
+#pragma unroll
+        for (int c = 0; c < 16; ++c) {
+            cd rs;  // the scaled pivot row; its column j becomes 1 / pivot
+            if (c == j) rs = inv;
+            else rs = grape::cmulf(grape::cmake(__shfl(ar[c], p, 64), __shfl(ai[c], p, 64)), inv);
+            const double br = c == j ? 0.0 : ar[c], bi = c == j ? 0.0 : ai[c];
+            const double nr = fma(-mr, rs.re, fma(mi, rs.im, br));
+            const double ni = fma(-mr, rs.im, fma(-mi, rs.re, bi));
+            ar[c] = isp ? rs.re : nr;
+            ai[c] = isp ? rs.im : ni;
+        }
+        if (isp) {
+            used = true;
+            myj = j;
+        }
+        // one step at a time (as wave_inv16)
+#pragma unroll
+        for (int c = 0; c < 16; ++c) asm volatile("" : "+v"(ar[c]), "+v"(ai[c]));
+    }
+    double *gr = buf + PV_G, *gi = gr + 4 * SMALL;
+#pragma unroll
+    for (int c = 0; c < 16; ++c) {
+        gr[sidx16(l, c)] = ar[c];
+        gi[sidx16(l, c)] = ai[c];
+    }
+    ibuf[PV_PJ + l] = myj;
+    if (myj >= 0) ibuf[PV_PERM + 16 * kb + myj] = l;
+}
+
+__device__ __forceinline__ void gj_solve_pivot(HM &Q, HM &Pm, double *lds, const Lane &ln_in, bool &singular) {
+    double *buf = lds + LDS_R0;
+    int *ibuf = reinterpret_cast<int *>(lds + LDS_R1);
+    double *panr = buf + PV_PAN, *pani = panr + 4 * SMALL;
+    const double *gr = buf + PV_G, *gi = gr + 4 * SMALL;
+    double *qr = buf + PV_PRQ, *qi = qr + 4 * SMALL;
+    double *pr = buf + PV_PRP, *pi = pr + 4 * SMALL;
+    bool used = false;  // wave 0: my row (= lane) has been a pivot row
+    __syncthreads();    // the matrix regions are free
+#pragma unroll 1  // one copy of the panel code (its 16 steps are unrolled)
+    for (int kb = 0; kb < NT; ++kb) {
+        const Lane ln = pinned(ln_in);
+        if (ln.w == kb) {
+#pragma unroll
+            for (int i = 0; i < 2; ++i)
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    const int o = sidx16(ln.row(i, r), ln.l & 15);
+                    panr[o] = Q.re[i][r];
+                    pani[o] = Q.im[i][r];
+                }
+        }
+        __syncthreads();
+        if (ln.wid == 0) pv_panel(buf, ibuf, kb, ln.l, used, singular);
+        __syncthreads();
+        const bool doq = ln.w > kb;  // Q's column blocks up to kb are never read again
+        int pj[2][4];
+#pragma unroll
+        for (int i = 0; i < 2; ++i)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int j = ibuf[PV_PJ + ln.row(i, r)];
+                pj[i][r] = j;
+                if (j >= 0) {
+                    const int o = pv_pridx(j & 15, ln.col());
+                    pr[o] = Pm.re[i][r];
+                    pi[o] = Pm.im[i][r];
+                    if (doq) {
+                        qr[o] = Q.re[i][r];
+                        qi[o] = Q.im[i][r];
+                    }
+                }
+            }
+        __syncthreads();
+#pragma unroll
+        for (int i = 0; i < 2; ++i) {
+            const int t = ln.tile(i);
+#pragma unroll
+            for (int r = 0; r < 4; ++r)
+                if (pj[i][r] >= 0) {  // a pivot row keeps no term of its own
+                    Pm.re[i][r] = 0.0;
+                    Pm.im[i][r] = 0.0;
+                    Q.re[i][r] = 0.0;
+                    Q.im[i][r] = 0.0;
+                }
+#pragma unroll
+            for (int s = 0; s < 4; ++s) {
+                const int oa = sidx16(16 * t + (ln.l & 15), 4 * s + (ln.l >> 4));
+                const int ob = pv_pridx(4 * s + (ln.l >> 4), ln.col());
+                const double aR = gr[oa], aI = gi[oa];
+                cmfma1(Pm.re[i], Pm.im[i], aR, aI, pr[ob], pi[ob]);
+                if (doq) cmfma1(Q.re[i], Q.im[i], aR, aI, qr[ob], qi[ob]);
+            }
+        }
+        // no barrier here: the next step's panel store touches PV_PAN only, and its own barrier
+        // comes before anything read above is written again
+    }
+    // X[k] = Pm[perm[k]]
+    __syncthreads();
+    SM S0 = sm_at(lds, LDS_R0);
+    sm_store(S0, Pm, ln_in);
+    __syncthreads();
+    {
+        const Lane ln = pinned(ln_in);
+#pragma unroll
+        for (int i = 0; i < 2; ++i)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int src = ibuf[PV_PERM + ln.row(i, r)] & (N - 1);
+                const int o = sidx(src, ln.col());
+                Pm.re[i][r] = S0.re[o];
+                Pm.im[i][r] = S0.im[o];
+            }
+    }
+    __syncthreads();  // region 0 free again
+}
+
+// ---------------------------------------------------------------------------
 // Pade tables (Julia LinearAlgebra.exp!) and the degree choice
 // ---------------------------------------------------------------------------
 __constant__ const double kDPade[5][14] = {
@@ -714,7 +893,9 @@ __constant__ const double kDPade[5][14] = {
      10559470521600.0, 670442572800.0, 33522128640.0, 1323241920.0, 40840800.0, 960960.0, 16380.0, 182.0, 1.0}};
 
 // Julia's (m, s) for |A|_1, with the Pade-13 scaling raised until |A/2^s|_1 <= 1.6
-// (keeps Re q(i theta) > 0 with margin: no-interchange solve, see the header)
+// (keeps Re q(i theta) > 0 with margin: no-interchange solve, see the header).  Pivot: the pivoted
+// solve needs no such margin -- Julia's s = ceil(log2(|A|_1 / 5.4)) as it stands.
+template <bool Pivot = false>
 __device__ __forceinline__ int dense_pade_degree(double nA, int &s) {
     s = 0;
     if (nA <= 2.1) {
@@ -725,6 +906,7 @@ __device__ __forceinline__ int dense_pade_degree(double nA, int &s) {
     }
     const double l = log2(nA / 5.4);
     if (l > 0.0) s = (int)ceil(l);
+    if constexpr (Pivot) return 13;
     const double l2 = log2(nA / 1.6);
     const int s2 = l2 > 0.0 ? (int)ceil(l2) : 0;
     if (s2 > s) s = s2;
@@ -839,7 +1021,11 @@ __device__ __forceinline__ void wg_expm_taylor(const HM &A, int degree, HM &X, d
     __syncthreads();  // every wave done with the LDS regions
 }
 
-template <class Build>
+// Pivot = true: any A (a decay term -i Gamma / 2, a non-Hermitian error generator).  Pade 9 / 13
+// solve with gj_solve_pivot, Pade 13 scales as Julia does; the Taylor regime has no solve and is
+// valid for any A as it stands.  exp! balances A first; the device does not (as the small engine,
+// grape_device.hpp), so m and s come from the unbalanced 1-norm.
+template <bool Pivot = false, class Build>
 __device__ __forceinline__ int wg_expm(const Build &build, HM &X, double *lds, const Lane &ln, bool &singular) {
     SM S0 = sm_at(lds, LDS_R0), S1 = sm_at(lds, LDS_R1);
     int s = 0, m;
@@ -848,7 +1034,10 @@ __device__ __forceinline__ int wg_expm(const Build &build, HM &X, double *lds, c
         HM A;
         build(A);
         const double nA = wg_norm1(A, lds, ln);
-        m = dense_pade_degree(nA, s);
+        m = dense_pade_degree<Pivot>(nA, s);
+        // |A|_1 is the same in every lane: a scalar m keeps the Pade branches scalar.  (Not s: with a
+        // scalar squaring count the register allocator spilled three dwords around the squaring loop.)
+        if constexpr (Pivot) m = __builtin_amdgcn_readfirstlane(m);
         if (s > 0) hm_scale(A, ldexp(1.0, -s));
         __syncthreads();
         sm_store(S0, A, ln);
@@ -973,7 +1162,8 @@ __device__ __forceinline__ int wg_expm(const Build &build, HM &X, double *lds, c
         V.re[i] = vr + ur;
         V.im[i] = vi + ui;
     }
-    gj_solve(U, V, lds, ln, singular);
+    if constexpr (Pivot) gj_solve_pivot(U, V, lds, ln, singular);
+    else gj_solve(U, V, lds, ln, singular);
     for (int q = 0; q < s; ++q) {
         sm_store(S0, V, ln);
         __syncthreads();

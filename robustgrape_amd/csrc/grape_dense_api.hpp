@@ -54,13 +54,16 @@ constexpr int kImgDoubles = 2 * 64 * 64;
 // Pipeline of one batch (k_dexp, k_dscan, k_dcarry, k_dmc, k_dgrad) on `st`.
 hipError_t launch_pipeline(const DenseProblem &P, const DenseBatch &B, hipStream_t st,
                            const grape_host::KMark &mark);
-// n exponentials of padded images (grape_expm_batch for 12 < d <= 64).
-hipError_t launch_expm_raw(const double *A, double *E, int n, int *status, int *mstats, hipStream_t st);
+// n exponentials of padded images (grape_expm_batch for 12 < d <= 64).  pivot: k_dexp_raw_piv, the
+// pivoted Pade solve for a general A (grape_expm_batch_general); false needs a skew-Hermitian A.
+hipError_t launch_expm_raw(const double *A, double *E, int n, int *status, int *mstats, hipStream_t st,
+                           bool pivot = false);
 hipError_t set_lds_limits();
 // Every variant P.vs[0..P.nv) of every step of ONE evaluation (B.nb = 1): k_dexp into the
 // images B.E, then converted to row-major d x d tiles rows[Nt][nv][D][D] (the table the
-// materialised-derivative kernels of grape_unitary.hip read).
-hipError_t launch_variant_table(const DenseProblem &P, const DenseBatch &B, grape::cd *rows, hipStream_t st);
+// materialised-derivative kernels of grape_unitary.hip read).  pivot: k_dexp_piv (general H0 / Herror).
+hipError_t launch_variant_table(const DenseProblem &P, const DenseBatch &B, grape::cd *rows, hipStream_t st,
+                                bool pivot = false);
 // Time sharding: one evaluation (B.nb = 1) of a slice plan.  Forward: the slice's
 // propagators, chunk prefixes and carries (kept in B) and its total U_slice into Ucols (column-major
 // d x d).  Gradient: M' (column-major) replaces the plan's M = G U, then k_dmc / k_dgrad give the
@@ -69,8 +72,9 @@ hipError_t launch_slice_forward(const DenseProblem &P, const DenseBatch &B, grap
 hipError_t launch_slice_gradient(const DenseProblem &P, const DenseBatch &B, const grape::cd *Mcols, hipStream_t st);
 // Closure fallback above GRAPE_MAX_SMALL_DIM: n host-tabulated H (column-major d x d) -> exp(-i dt H)
 // as row-major d x d tiles (`rows`), through the padded images Aimg / Eimg (n images each); the
-// no-interchange solve needs a Hermitian H (checked on the host, robustgrape_amd/engine.py)
+// no-interchange solve needs a Hermitian H (checked on the host, robustgrape_amd/engine.py); pivot:
+// k_dexp_raw_piv, any H (plans created with GRAPE_OPT_GENERAL_H0)
 hipError_t launch_table_variants(const grape::cd *H, int D, int n, double dt, double *Aimg, double *Eimg,
-                                 grape::cd *rows, int *status, hipStream_t st);
+                                 grape::cd *rows, int *status, hipStream_t st, bool pivot = false);
 
 }  // namespace grape_dense

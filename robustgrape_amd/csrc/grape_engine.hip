@@ -300,6 +300,9 @@ struct grape_plan {
     // (UnitaryCalculations.jl:47) and the fidelity path runs from the materialised derivatives
     // (grape_unitary.hip k_u_fid_head / k_u_fid_contract), one evaluation at a time
     bool general_h0 = false;
+    // 12 < d <= 64 created with GRAPE_OPT_GENERAL_H0: every exponential through the dense engine's
+    // pivoted kernels (k_dexp_piv / k_dexp_raw_piv), valid for any generator
+    bool pivot = false;
     cd *ud_Ci = nullptr, *d_G = nullptr;
     cd *d_fscr = nullptr;        // d > 12: the fidelity head's tiles (global scratch)
     double *ud_Aimg = nullptr;   // closures at d > 12: the tabulated generators as padded images
@@ -1247,8 +1250,10 @@ int grape_plan_create(const grape_desc *desc, int device, grape_plan **out) {
         if (rc != GRAPE_ERR_UNSUPPORTED || D > GRAPE_MAX_SMALL_DIM) return rc;
         general_h0 = true;  // non-Hermitian H0: the general path serves it
     }
-    if (general_h0 && D > GRAPE_MAX_SMALL_DIM && !tables)
-        return fail(GRAPE_ERR_UNSUPPORTED, "general (non-Hermitian) H0: ndim <= GRAPE_MAX_SMALL_DIM only");
+    // 12 < d <= 64 with the option: the general path over the dense engine's pivoted exponential
+    // (operator bases: below, after the general-path problem; host tables: launch_table_variants).
+    // Without the option nothing changes: a non-Hermitian H0 or error source is refused above.
+    const bool pivot = general_h0 && D > GRAPE_MAX_SMALL_DIM;
     // closures above the small engine: host tables through the general path (materialised
     // derivatives), each tabulated generator exponentiated by the dense engine (grape_dense.hip
     // launch_table_variants; the host checks that the tables are Hermitian)
@@ -1285,7 +1290,8 @@ int grape_plan_create(const grape_desc *desc, int device, grape_plan **out) {
     if (hipHostMalloc(reinterpret_cast<void **>(&p->h_status), sizeof(int), hipHostMallocDefault) != hipSuccess)
         return bail(fail(GRAPE_ERR_ALLOC, "pinned allocation failed"));
     *p->h_status = 0;
-    if (D > GRAPE_MAX_SMALL_DIM && !tables) {
+    p->pivot = pivot;
+    if (D > GRAPE_MAX_SMALL_DIM && !tables && !pivot) {
         const int rcd = create_dense(desc, p, xadd_dep, ps, n_err_terms);
         if (rcd) return bail(rcd);
         *out = p;
@@ -1755,6 +1761,21 @@ int grape_plan_create(const grape_desc *desc, int device, grape_plan **out) {
                              hipEventCreateWithFlags(&p->ev_fork, hipEventDisableTiming) != hipSuccess ||
                              hipEventCreateWithFlags(&p->ev_join, hipEventDisableTiming) != hipSuccess))
             return bail(fail(GRAPE_ERR_HIP, "cannot create the auxiliary stream"));
+    }
+    if (pivot && !tables) {
+        // the operator images and the problem ud_propagators_dev's dense branch exponentiates from
+        // (k_dexp_piv over the variant list): the terms, scalars and x layout are the general path's
+        if (grape_dense::set_lds_limits() != hipSuccess) return bail(fail(GRAPE_ERR_HIP, "cannot raise LDS limit (dense)"));
+        const size_t IMG = grape_dense::kImgDoubles;
+        std::vector<double> img((size_t)n_ops * IMG);
+        for (int o = 0; o < n_ops; ++o) to_dense_image(desc->ops + 2 * (size_t)o * D * D, D, img.data() + o * IMG);
+        if (dalloc(&p->dn_opimg, img.size()) != hipSuccess ||
+            hipMemcpy(p->dn_opimg, img.data(), img.size() * sizeof(double), hipMemcpyHostToDevice) != hipSuccess)
+            return bail(fail(GRAPE_ERR_ALLOC, "device allocation failed (dense operator images)"));
+        p->DP = grape_dense::DenseProblem{};
+        p->DP.P = P;
+        p->DP.opimg = p->dn_opimg;
+        p->dense = true;
     }
     *out = p;
     return GRAPE_OK;
@@ -2523,10 +2544,10 @@ static int ud_propagators_dev(grape_plan *p, const double *d_x, int nv, const cd
         DB.x = d_x;
         DB.E = p->ud_Eimg;
         DB.status = p->d_ctrl + 2;
-        HIPCHECK(grape_dense::launch_variant_table(DPu, DB, p->ud_E, st));
+        HIPCHECK(grape_dense::launch_variant_table(DPu, DB, p->ud_E, st, p->pivot));
     } else if (d_Htab && P0.D > GRAPE_MAX_SMALL_DIM) {  // closures above the small engine
         HIPCHECK(grape_dense::launch_table_variants(d_Htab, P0.D, P0.Nt * nv, P0.dt, p->ud_Aimg, p->ud_Eimg, p->ud_E,
-                                                   p->d_ctrl + 2, st));
+                                                   p->d_ctrl + 2, st, p->pivot));
     } else if (d_Htab) {
         Bu.Htab = d_Htab;
         HIPCHECK(dispatch_expm_table(P0.D, Pu, Bu, st));
@@ -2771,7 +2792,7 @@ int grape_unitary_derivs_tables(grape_plan *p, const double *x, const double *H,
     return unitary_derivs(p, x, H, U, U_dx, U_dx_add, U_derr, U_derr_dx, U_derr_dx_add);
 }
 
-static int dense_expm_batch(int device, int ndim, int n, const double *A, double *E, int *stats) {
+static int dense_expm_batch(int device, int ndim, int n, const double *A, double *E, int *stats, bool pivot) {
     const size_t IMG = grape_dense::kImgDoubles;
     std::vector<double> h((size_t)n * IMG);
     for (int i = 0; i < n; ++i) to_dense_image(A + 2 * (size_t)i * ndim * ndim, ndim, h.data() + i * IMG);
@@ -2789,7 +2810,7 @@ static int dense_expm_batch(int device, int ndim, int n, const double *A, double
     if (grape_dense::set_lds_limits() != hipSuccess ||
         hipMemcpy(dA, h.data(), h.size() * sizeof(double), hipMemcpyHostToDevice) != hipSuccess ||
         hipMemset(dctrl, 0, 8 * sizeof(int)) != hipSuccess ||
-        grape_dense::launch_expm_raw(dA, dE, n, dctrl + 1, dctrl + 2, nullptr) != hipSuccess ||
+        grape_dense::launch_expm_raw(dA, dE, n, dctrl + 1, dctrl + 2, nullptr, pivot) != hipSuccess ||
         hipDeviceSynchronize() != hipSuccess ||
         hipMemcpy(h.data(), dE, h.size() * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess ||
         hipMemcpy(ctrl, dctrl, 8 * sizeof(int), hipMemcpyDeviceToHost) != hipSuccess)
@@ -2803,7 +2824,7 @@ static int dense_expm_batch(int device, int ndim, int n, const double *A, double
     return GRAPE_OK;
 }
 
-int grape_expm_batch(int device, int ndim, int n, const double *A, double *E, int *stats) {
+static int expm_batch(int device, int ndim, int n, const double *A, double *E, int *stats, bool pivot) {
     if (ndim < 2 || ndim > GRAPE_MAX_DENSE_DIM) return fail(GRAPE_ERR_UNSUPPORTED, "ndim outside [2, GRAPE_MAX_DENSE_DIM]");
     if (ndim > GRAPE_MAX_SMALL_DIM) {
         if (n < 0 || (n > 0 && (!A || !E))) return fail(GRAPE_ERR_INVALID, "bad argument");
@@ -2811,7 +2832,7 @@ int grape_expm_batch(int device, int ndim, int n, const double *A, double *E, in
         int ndev = 0;
         if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return fail(GRAPE_ERR_NO_DEVICE, "no HIP device");
         HIPCHECK(hipSetDevice(device));
-        return dense_expm_batch(device, ndim, n, A, E, stats);
+        return dense_expm_batch(device, ndim, n, A, E, stats, pivot);
     }
     if (n < 0 || (n > 0 && (!A || !E))) return fail(GRAPE_ERR_INVALID, "bad argument");
     if (n == 0) return GRAPE_OK;
@@ -2844,6 +2865,14 @@ int grape_expm_batch(int device, int ndim, int n, const double *A, double *E, in
         for (int k = 0; k < 5; ++k) stats[k] = ctrl[2 + k];
     if (ctrl[1] & 1) return fail(GRAPE_ERR_SINGULAR, "singular Pade denominator");
     return GRAPE_OK;
+}
+
+int grape_expm_batch(int device, int ndim, int n, const double *A, double *E, int *stats) {
+    return expm_batch(device, ndim, n, A, E, stats, false);
+}
+
+int grape_expm_batch_general(int device, int ndim, int n, const double *A, double *E, int *stats) {
+    return expm_batch(device, ndim, n, A, E, stats, true);
 }
 
 }  // extern "C"

@@ -20,13 +20,23 @@ from .tables import SharedTables, get_workers, host_tables, is_hermitian_h0, tab
 from .types import FidelityRobustGRAPEProblem, split_x
 
 
+# get_plan's request for general_fallback (below): it creates its plans as
+# GrapePlan(fp, nparam, device, max_batch), so the request travels as this thread's default
+_plan_defaults = threading.local()
+
+
 class GrapePlan:
     """One device plan for one problem (grape_plan_create / grape_plan_destroy)."""
 
     def __init__(self, fp: FidelityRobustGRAPEProblem, nparam: int, device: int = 0, max_batch: int = 256,
-                 options: int = 0, scan_waves: int = 0):
+                 options: int = 0, scan_waves: int = 0, general_fallback: bool | None = None):
         """options: GRAPE_OPT_* flags (operators.OPT_*), scan_waves: k_scan width override --
-        plan-creation choices between implementations of the same outputs (include/grape.h)."""
+        plan-creation choices between implementations of the same outputs (include/grape.h).
+        general_fallback: at 12 < ndim <= 64 a problem the default plan refuses or cannot serve (a
+        non-Hermitian H0 or error generator) moves to the general path with the pivoted dense
+        exponential (OPT_GENERAL_H0) instead of raising.  Default: False, except inside get_plan."""
+        if general_fallback is None:
+            general_fallback = getattr(_plan_defaults, "general_fallback", False)
         L = _capi.lib()
         self.fp = fp
         self.up = fp.unitary_problem
@@ -37,6 +47,7 @@ class GrapePlan:
         self.max_batch = int(max_batch)
         self.requested_batch = self.max_batch  # before the closure-table byte cap (get_plan's key)
         self.options = int(options)
+        self.general_fallback = bool(general_fallback) and 12 < self.up.ndim <= 64
         self.lock = threading.Lock()  # one evaluation at a time (the plan's buffers are shared)
         self._shared = None  # closure fallback: double-buffered shared-memory tables
         # operator bases -> the fused device path; plain closures -> the host-table fallback
@@ -49,26 +60,18 @@ class GrapePlan:
         else:
             self._bufs = DescriptorBuffers(fp, self.nparam, self.max_batch, options, scan_waves)
         h = ctypes.c_void_p()
-        _capi.check(L.grape_plan_create(ctypes.byref(self._bufs.desc), self.device, ctypes.byref(h)))
+        rc = L.grape_plan_create(ctypes.byref(self._bufs.desc), self.device, ctypes.byref(h))
+        if rc == _capi.ERR_UNSUPPORTED and self.general_fallback and not (self.options & OPT_GENERAL_H0):
+            # refused as it stands (non-Hermitian H0 or error source above 12 levels): once more, general
+            self.options |= OPT_GENERAL_H0
+            self._bufs.desc.reserved[1] = self.options
+            rc = L.grape_plan_create(ctypes.byref(self._bufs.desc), self.device, ctypes.byref(h))
+        _capi.check(rc)
         self.handle = h
         self._stream_ptr = None
 
-    def general_h0_for(self, H0s, Hall=None):
-        """Closure plans: the host sees H0 only as tables; a non-Hermitian nominal H0 (e.g. a
-        -i Gamma/2 decay term) recreates the plan on the general-H0 path (GRAPE_OPT_GENERAL_H0,
-        the reference's LU-inverted chain, UnitaryCalculations.jl:47) before the device call.
-        Above 12 levels every tabulated generator Hall (default H0s) goes through the dense
-        engine's interchange-free solve, which needs it Hermitian: anything else is refused.
-        H0s / Hall: matrices (any leading shape, either storage order)."""
-        if not self.tables:
-            return
-        if self.up.ndim > 12:
-            if not is_hermitian_h0(H0s if Hall is None else Hall):
-                raise ValueError("closure problems above 12 levels need Hermitian H0 / H0 + Herror tables "
-                                 "(the dense engine's exponential); non-Hermitian generators are served up to 12 levels")
-            return
-        if (self.options & OPT_GENERAL_H0) or is_hermitian_h0(H0s):
-            return
+    def _recreate_general(self):
+        """The same descriptor with OPT_GENERAL_H0, in place of the current plan."""
         self.options |= OPT_GENERAL_H0
         self._bufs.desc.reserved[1] = self.options
         h = ctypes.c_void_p()
@@ -77,6 +80,30 @@ class GrapePlan:
         self.handle = h
         if self._stream_ptr:
             self.set_stream(self._stream_ptr)
+
+    def general_h0_for(self, H0s, Hall=None):
+        """Closure plans: the host sees H0 only as tables; a non-Hermitian nominal H0 (e.g. a
+        -i Gamma/2 decay term) recreates the plan on the general-H0 path (GRAPE_OPT_GENERAL_H0,
+        the reference's LU-inverted chain, UnitaryCalculations.jl:47) before the device call.
+        Above 12 levels every tabulated generator Hall (default H0s) goes through the dense
+        engine's interchange-free solve, which needs it Hermitian: anything else is refused,
+        unless the plan has OPT_GENERAL_H0 (the pivoted exponential serves any table) or was
+        created with general_fallback, which recreates it with that option.
+        H0s / Hall: matrices (any leading shape, either storage order)."""
+        if not self.tables:
+            return
+        if self.up.ndim > 12:
+            if (self.options & OPT_GENERAL_H0) or is_hermitian_h0(H0s if Hall is None else Hall):
+                return
+            if self.general_fallback:
+                self._recreate_general()
+                return
+            raise ValueError("closure problems above 12 levels need Hermitian H0 / H0 + Herror tables "
+                             "(the dense engine's exponential) unless the plan has OPT_GENERAL_H0; "
+                             "without it non-Hermitian generators are served up to 12 levels")
+        if (self.options & OPT_GENERAL_H0) or is_hermitian_h0(H0s):
+            return
+        self._recreate_general()
 
     def close(self):
         if getattr(self, "handle", None) is not None and self.handle.value:
@@ -281,7 +308,11 @@ def get_plan(fp: FidelityRobustGRAPEProblem, nparam: int, device: int = 0, max_b
                 ent.close()
             if ent.fp is fp:
                 want = max(want, ent.requested_batch)
-        plan = GrapePlan(fp, nparam, device, want)
+        _plan_defaults.general_fallback = True  # the public functions serve non-Hermitian problems above 12 levels
+        try:
+            plan = GrapePlan(fp, nparam, device, want)
+        finally:
+            _plan_defaults.general_fallback = False
         _plan_cache[key] = plan
         while len(_plan_cache) > MAX_CACHED_PLANS:
             _, old = _plan_cache.popitem(last=False)
