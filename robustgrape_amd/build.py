@@ -31,7 +31,7 @@ DEPS = SOURCES + [os.path.join(CSRC, f) for f in
                   ("grape_device.hpp", "grape_kernels.hpp", "grape_errpath.hpp", "grape_launch.hpp", "grape_lane.hpp",
                    "grape_walk.hpp", "grape_walk_api.hpp", "grape_eval1_api.hpp",
                    "grape_dense.hpp", "grape_dense_api.hpp", "grape_unitary_api.hpp",
-                   "grape_projector_api.hpp")] + \
+                   "grape_projector_api.hpp", "grape_plan_setup.hpp")] + \
     [os.path.join(ROOT, "include", "grape.h")]
 
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")

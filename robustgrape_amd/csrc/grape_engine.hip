@@ -13,6 +13,7 @@
 #include <cstdio>
 #include <cstring>
 #include <string>
+#include <type_traits>
 #include <cstdlib>
 #include <csignal>
 #include <cstdint>
@@ -29,6 +30,7 @@
 #include "grape_unitary_api.hpp"
 #include "grape_symmetry.hpp"
 #include "grape_eval1_api.hpp"
+#include "grape_plan_setup.hpp"
 
 // instantiated in grape_inst.hip (one translation unit per dimension)
 namespace grape_host {
@@ -145,70 +147,40 @@ using grape_host::launch_pipeline;
 using grape_host::launch_expm_raw;
 using grape_host::set_lds_limits;
 
-
-hipError_t dispatch_pipeline(int D, const DevProblem &P, const DevBatch &B, hipStream_t st, const KMark &mk) {
+// f(std::integral_constant<int, D>) for the instantiated dimension D (GRAPE_DIMS)
+template <class F>
+hipError_t dispatch_dim(int D, F &&f) {
     switch (D) {
 #define CASE(d) \
-    case d: return launch_pipeline<d>(P, B, st, mk);
+    case d: return f(std::integral_constant<int, d>{});
         GRAPE_DIMS(CASE)
 #undef CASE
     }
     return hipErrorInvalidValue;
+}
+hipError_t dispatch_pipeline(int D, const DevProblem &P, const DevBatch &B, hipStream_t st, const KMark &mk) {
+    return dispatch_dim(D, [&](auto d) { return launch_pipeline<decltype(d)::value>(P, B, st, mk); });
 }
 hipError_t dispatch_sector_stage(int S, int stage, const DevProblem &P, const DevBatch &B, hipStream_t st,
                                  const KMark &mk) {
-    switch (S) {
-#define CASE(d) \
-    case d: return grape_host::launch_sector_stage<d>(stage, P, B, st, mk);
-        GRAPE_DIMS(CASE)
-#undef CASE
-    }
-    return hipErrorInvalidValue;
+    return dispatch_dim(S, [&](auto d) { return grape_host::launch_sector_stage<decltype(d)::value>(stage, P, B, st, mk); });
 }
 hipError_t dispatch_sector_reduce(int S, const DevProblem &P, const DevBatch &B, const grape::SecParts &sp, int nev,
                                   hipStream_t st, const KMark &mk) {
-    switch (S) {
-#define CASE(d) \
-    case d: return grape_host::launch_sector_reduce<d>(P, B, sp, nev, st, mk);
-        GRAPE_DIMS(CASE)
-#undef CASE
-    }
-    return hipErrorInvalidValue;
+    return dispatch_dim(S, [&](auto d) { return grape_host::launch_sector_reduce<decltype(d)::value>(P, B, sp, nev, st, mk); });
 }
 hipError_t dispatch_expm_raw(int D, const cd *A, cd *E, int n, int *ovf, int *ovfc, int *status,
                              int *mstats, hipStream_t st) {
-    switch (D) {
-#define CASE(d) \
-    case d: return launch_expm_raw<d>(A, E, n, ovf, ovfc, status, mstats, st);
-        GRAPE_DIMS(CASE)
-#undef CASE
-    }
-    return hipErrorInvalidValue;
+    return dispatch_dim(D, [&](auto d) { return launch_expm_raw<decltype(d)::value>(A, E, n, ovf, ovfc, status, mstats, st); });
 }
 hipError_t dispatch_expm_variants(int D, const DevProblem &P, const DevBatch &B, hipStream_t st) {
-    switch (D) {
-#define CASE(d) \
-    case d: return grape_host::launch_expm_variants<d>(P, B, st);
-        GRAPE_DIMS(CASE)
-#undef CASE
-    }
-    return hipErrorInvalidValue;
+    return dispatch_dim(D, [&](auto d) { return grape_host::launch_expm_variants<decltype(d)::value>(P, B, st); });
+}
+hipError_t dispatch_expm_table(int D, const DevProblem &P, const DevBatch &B, hipStream_t st) {
+    return dispatch_dim(D, [&](auto d) { return grape_host::launch_expm_table<decltype(d)::value>(P, B, st); });
 }
 hipError_t dispatch_lds_limits(int D) {
-    switch (D) {
-#define CASE(d) \
-    case d: return set_lds_limits<d>();
-        GRAPE_DIMS(CASE)
-#undef CASE
-    }
-    return hipErrorInvalidValue;
-}
-
-template <typename T>
-hipError_t dalloc(T **p, size_t n) {
-    *p = nullptr;
-    if (n == 0) n = 1;
-    return hipMalloc(reinterpret_cast<void **>(p), n * sizeof(T));
+    return dispatch_dim(D, [&](auto d) { return set_lds_limits<decltype(d)::value>(); });
 }
 
 }  // namespace
@@ -221,7 +193,7 @@ struct grape_plan {
     int *h_status = nullptr;           // pinned copy of the device status word
     DevProblem P{};
     int max_batch = 0;
-    // device buffers
+    grape_setup::DevicePool mem;  // owns every device buffer of the plan; the named pointers below are views
     cd *d_ops = nullptr;
     cd *d_opsT = nullptr;
     Term *d_h0 = nullptr, *d_tgt = nullptr, *d_err = nullptr;
@@ -363,24 +335,7 @@ static void free_plan(grape_plan *p) {
         }
         (void)hipHostFree(p->e1_trace);
     }
-    void *bufs[] = {p->d_ops, p->d_opsT, p->d_h0, p->d_tgt, p->d_err, p->d_err_off, p->d_W, p->d_E, p->d_Q, p->d_Mc,
-                    p->d_x, p->d_F, p->d_Fdx, p->d_part, p->d_tgt_part, p->d_ovf, p->d_ctrl, p->d_sink,
-                    p->d_Carry, p->d_Ub, p->d_Me, p->d_vs, p->d_Fd2, p->d_Fd2dx, p->d_part_err, p->d_Zl, p->d_ovf2, p->d_ovf2_slots,
-                    p->dn_opimg, p->dn_W, p->dn_E, p->dn_Q, p->dn_Carry, p->dn_M, p->dn_Mc, p->dn_Z,
-                    p->dn_Ub, p->dn_Zl, p->dn_Vc, p->dn_Sx, p->dn_Tot, p->dn_Me, p->dn_Mp, p->dn_B0, p->dn_Fadd, p->dn_Fd2add,
-                    p->ud_vs, p->ud_E, p->ud_C, p->ud_V, p->ud_S, p->ud_out, p->ud_ovf, p->ud_gscr, p->ud_Eimg,
-                    p->ud_Ci, p->d_G, p->d_xT, p->d_fscr, p->ud_Aimg,
-                    p->d_Htab, p->d_U0tab, p->d_PA, p->d_PB, p->d_P0g, p->d_gpscr,
-                    p->d_fixed, p->d_gout, p->d_slice, p->d_ops_sym, p->d_opsT_sym, p->d_PA_sym, p->d_PB_sym,
-                    p->d_W_sym, p->d_e1_Et, p->d_e1_scr, p->d_e1_tab};
-    for (void *b : bufs)
-        if (b) (void)hipFree(b);
-    for (auto &c : p->sb) {
-        void *sbufs[] = {c.E, c.Q, c.Mc, c.Carry, c.Ub, c.slots, c.ops, c.opsT, c.Msec, c.ovf, c.ovf2, c.sidx, c.part,
-                         c.Zl, c.Me, c.TotS, c.MsecE, c.part_err, c.Tc, c.wscr, c.Ew, c.Wc, c.gauge_n, c.gEt};
-        for (void *b : sbufs)
-            if (b) (void)hipFree(b);
-    }
+    p->mem.release_all();
     for (auto &e : p->ev_pool) (void)hipEventDestroy(e);
     for (auto &pe : p->pending) {
         (void)hipEventDestroy(pe.a);
@@ -507,32 +462,28 @@ static int check_hermitian_terms(const grape_desc *desc, const grape_term *t, in
 // ---------------------------------------------------------------------------
 // dense engine plan (GRAPE_MAX_SMALL_DIM < d <= GRAPE_MAX_DENSE_DIM)
 // ---------------------------------------------------------------------------
-// column-major interleaved d x d complex -> zero-padded 64 x 64 register-file image
-static void to_dense_image(const double *src, int d, double *img) {
-    const int P = 64 * 64;
+// column-major interleaved d x d complex <-> zero-padded 64 x 64 register-file image:
+// f(o, e) for every image slot o (re at o, im at 64 * 64 + o) and its element's offset e (-1: padding)
+template <class F>
+static void dense_image_slots(int d, F &&f) {
     for (int w = 0; w < 4; ++w)
         for (int t = 0; t < 4; ++t)
             for (int r = 0; r < 4; ++r)
                 for (int l = 0; l < 64; ++l) {
                     const int row = 16 * t + (l >> 4) + 4 * r, col = 16 * w + (l & 15);
-                    const int o = ((w * 4 + t) * 4 + r) * 64 + l;
-                    const bool in = row < d && col < d;
-                    img[o] = in ? src[2 * ((size_t)row + (size_t)col * d)] : 0.0;
-                    img[P + o] = in ? src[2 * ((size_t)row + (size_t)col * d) + 1] : 0.0;
+                    f(((w * 4 + t) * 4 + r) * 64 + l, row < d && col < d ? 2 * ((long)row + (long)col * d) : -1L);
                 }
 }
+static void to_dense_image(const double *src, int d, double *img) {
+    dense_image_slots(d, [&](int o, long e) {
+        img[o] = e >= 0 ? src[e] : 0.0;
+        img[64 * 64 + o] = e >= 0 ? src[e + 1] : 0.0;
+    });
+}
 static void from_dense_image(const double *img, int d, double *dst) {
-    const int P = 64 * 64;
-    for (int w = 0; w < 4; ++w)
-        for (int t = 0; t < 4; ++t)
-            for (int r = 0; r < 4; ++r)
-                for (int l = 0; l < 64; ++l) {
-                    const int row = 16 * t + (l >> 4) + 4 * r, col = 16 * w + (l & 15);
-                    if (row >= d || col >= d) continue;
-                    const int o = ((w * 4 + t) * 4 + r) * 64 + l;
-                    dst[2 * ((size_t)row + (size_t)col * d)] = img[o];
-                    dst[2 * ((size_t)row + (size_t)col * d) + 1] = img[P + o];
-                }
+    dense_image_slots(d, [&](int o, long e) {
+        if (e >= 0) dst[e] = img[o], dst[e + 1] = img[64 * 64 + o];
+    });
 }
 
 // The projector (FidelityCalculations.jl:47-51): the full matrix P0 when given, else its
@@ -544,46 +495,65 @@ struct ProjectorSetup {
     std::vector<cd> A, B, P0;
     bool general = false;
     double trP = 0.0;
+    void set_general(int D, const std::vector<cd> &pattern) {  // B = the pattern P, A = P0 P
+        std::fill(W.begin(), W.end(), 0.0);  // the specialised results are all overwritten
+        B = pattern;
+        A.assign((size_t)D * D, cd{0.0, 0.0});
+        for (int i = 0; i < D; ++i)
+            for (int j = 0; j < D; ++j)
+                for (int l = 0; l < D; ++l) {
+                    const cd a = P0[(size_t)i * D + l], b = B[(size_t)l * D + j];
+                    A[(size_t)i * D + j].re += a.re * b.re - a.im * b.im;
+                    A[(size_t)i * D + j].im += a.re * b.im + a.im * b.re;
+                }
+    }
 };
-static ProjectorSetup setup_projector(const grape_desc *desc) {
+// P0 and its pattern P = P0 .!= 0 as column-major interleaved matrices
+static void projector_matrices(const grape_desc *desc, std::vector<double> &P0, std::vector<double> &Pp) {
     const int D = desc->ndim;
+    P0.assign(2 * (size_t)D * D, 0.0);
+    Pp.assign(P0.size(), 0.0);
+    for (int j = 0; j < D; ++j)
+        for (int i = 0; i < D; ++i) {
+            const size_t t = 2 * (i + (size_t)j * D);
+            if (desc->projector) {
+                P0[t] = desc->projector[t];
+                P0[t + 1] = desc->projector[t + 1];
+            } else if (i == j) {
+                P0[t] = desc->projector_diag[i];
+            }
+            Pp[t] = (P0[t] != 0.0 || P0[t + 1] != 0.0) ? 1.0 : 0.0;
+        }
+}
+// ... the setup from them (the caller's, or rotated ones: the symmetry-adapted sectors, whose pattern
+// is the rotated P, not the pattern of the rotated P0)
+static ProjectorSetup projector_from(const double *P0, const double *Pp, int D) {
     ProjectorSetup ps;
     ps.W.assign(D, 0.0);
-    if (!desc->projector) {
-        for (int i = 0; i < D; ++i) {
-            ps.W[i] = desc->projector_diag[i];
-            ps.trP += desc->projector_diag[i];
-        }
-        return ps;
-    }
-    const double *P0 = desc->projector;
     ps.P0.resize((size_t)D * D);
+    std::vector<cd> B((size_t)D * D);
     for (int i = 0; i < D; ++i)
-        for (int j = 0; j < D; ++j) {
-            const cd v{P0[2 * ((size_t)i + (size_t)j * D)], P0[2 * ((size_t)i + (size_t)j * D) + 1]};
-            ps.P0[(size_t)i * D + j] = v;
+        for (int j = 0; j < D; ++j) {  // row-major tiles
+            const size_t t = 2 * (i + (size_t)j * D);
+            ps.P0[(size_t)i * D + j] = cd{P0[t], P0[t + 1]};
+            B[(size_t)i * D + j] = cd{Pp[t], Pp[t + 1]};
             if (i == j) {
-                ps.trP += v.re;
-                ps.W[i] = v.re;
-                if (v.im != 0.0) ps.general = true;
-            } else if (v.re != 0.0 || v.im != 0.0) {
+                ps.trP += P0[t];
+                ps.W[i] = P0[t];
+                // the diagonal specialisation needs P = diag(P0 != 0) exactly
+                const double pat = P0[t] != 0.0 ? 1.0 : 0.0;
+                if (P0[t + 1] != 0.0 || Pp[t + 1] != 0.0 || std::fabs(Pp[t] - pat) > 1e-14) ps.general = true;
+            } else if (P0[t] != 0.0 || P0[t + 1] != 0.0 || Pp[t] != 0.0 || Pp[t + 1] != 0.0) {
                 ps.general = true;
             }
         }
-    if (!ps.general) return ps;
-    std::fill(ps.W.begin(), ps.W.end(), 0.0);  // the specialised results are all overwritten
-    ps.B.resize((size_t)D * D);
-    ps.A.assign((size_t)D * D, cd{0.0, 0.0});
-    for (size_t t = 0; t < ps.B.size(); ++t)
-        ps.B[t] = cd{(ps.P0[t].re != 0.0 || ps.P0[t].im != 0.0) ? 1.0 : 0.0, 0.0};
-    for (int i = 0; i < D; ++i)
-        for (int j = 0; j < D; ++j)
-            for (int l = 0; l < D; ++l) {
-                const cd a = ps.P0[(size_t)i * D + l], b = ps.B[(size_t)l * D + j];
-                ps.A[(size_t)i * D + j].re += a.re * b.re - a.im * b.im;
-                ps.A[(size_t)i * D + j].im += a.re * b.im + a.im * b.re;
-            }
+    if (ps.general) ps.set_general(D, B);
     return ps;
+}
+static ProjectorSetup setup_projector(const grape_desc *desc) {
+    std::vector<double> P0, Pp;
+    projector_matrices(desc, P0, Pp);
+    return projector_from(P0.data(), Pp.data(), desc->ndim);
 }
 
 // uploads the general-projector matrices and sets P.gen_proj / PA / PB / P0g
@@ -591,8 +561,8 @@ static int upload_projector(grape_plan *p, const ProjectorSetup &ps, DevProblem 
     P.gen_proj = ps.general ? 1 : 0;
     if (!ps.general) return GRAPE_OK;
     const size_t T = ps.A.size();
-    if (dalloc(&p->d_PA, T) != hipSuccess || dalloc(&p->d_PB, T) != hipSuccess || dalloc(&p->d_P0g, T) != hipSuccess ||
-        dalloc(&p->d_gpscr, scratch_blocks * grape_proj::kScratchSlots * T) != hipSuccess)
+    if (p->mem.alloc(&p->d_PA, T) != hipSuccess || p->mem.alloc(&p->d_PB, T) != hipSuccess || p->mem.alloc(&p->d_P0g, T) != hipSuccess ||
+        p->mem.alloc(&p->d_gpscr, scratch_blocks * grape_proj::kScratchSlots * T) != hipSuccess)
         return fail(GRAPE_ERR_ALLOC, "device allocation failed (general projector)");
     if (hipMemcpy(p->d_PA, ps.A.data(), T * sizeof(cd), hipMemcpyHostToDevice) != hipSuccess ||
         hipMemcpy(p->d_PB, ps.B.data(), T * sizeof(cd), hipMemcpyHostToDevice) != hipSuccess ||
@@ -721,16 +691,6 @@ static SectorSetup find_sectors(const grape_desc *desc, bool tables) {
 // sector's coupling graph; the identity is then checked entry by entry at seven x values (a
 // rotated basis -- the symmetry-adapted sectors -- is covered: the blocks are the rotated ones).
 // On success N holds [nsec][S] charges >= 0 (0 on padding slots) and a the common factor.
-static std::complex<double> host_coef(const grape_term &t, double x) {
-    const double v = t.var == 1 ? x : 1.0;
-    const double arg = t.a * v + t.b;
-    std::complex<double> f(1.0, 0.0);
-    if (t.func == 1) f = arg;
-    else if (t.func == 2) f = std::cos(arg);
-    else if (t.func == 3) f = std::sin(arg);
-    else if (t.func == 4) f = std::complex<double>(std::cos(arg), std::sin(arg));
-    return std::complex<double>(t.scale_re, t.scale_im) * f;
-}
 static bool find_gauge(const grape_desc *desc, const grape_desc &sdesc, const SectorClass &sc, double &a,
                        std::vector<int> &N) {
     constexpr int kMaxCharge = 8;
@@ -759,7 +719,7 @@ static bool find_gauge(const grape_desc *desc, const grape_desc &sdesc, const Se
         H.assign((size_t)S * S, 0.0);
         for (int t = 0; t < lists[li].second; ++t) {
             const grape_term &tm = lists[li].first[t];
-            const std::complex<double> c = host_coef(tm, x);
+            const std::complex<double> c = term_value(tm, &x, nullptr, 0);  // (no x_add, no step index: checked above)
             for (int r = 0; r < S; ++r)
                 for (int q = 0; q < S; ++q) {
                     const int gi = sc.sidx[(size_t)w * S + r], gj = sc.sidx[(size_t)w * S + q];
@@ -900,53 +860,13 @@ static SymSetup symmetry_setup(const grape_desc *desc) {
         snap_residue(r, D, 1e-15);
     }
     // the projector P0 and its pattern P in the rotated basis
-    std::vector<double> P0(T2, 0.0), Pp(T2, 0.0), P0r(T2), Ppr(T2);
-    for (int j = 0; j < D; ++j)
-        for (int i = 0; i < D; ++i) {
-            const size_t t = 2 * (i + (size_t)j * D);
-            if (desc->projector) {
-                P0[t] = desc->projector[t];
-                P0[t + 1] = desc->projector[t + 1];
-            } else if (i == j) {
-                P0[t] = desc->projector_diag[i];
-            }
-            Pp[t] = (P0[t] != 0.0 || P0[t + 1] != 0.0) ? 1.0 : 0.0;
-        }
+    std::vector<double> P0, Pp, P0r(T2), Ppr(T2);
+    projector_matrices(desc, P0, Pp);
     grape_sym::rotate(sy.split, P0.data(), P0r.data());
     grape_sym::rotate(sy.split, Pp.data(), Ppr.data());
     snap_residue(P0r.data(), D, 1e-15);
     snap_residue(Ppr.data(), D, 1e-15);
-    ProjectorSetup &ps = sy.ps;
-    ps.W.assign(D, 0.0);
-    ps.P0.resize((size_t)D * D);
-    std::vector<cd> Br((size_t)D * D);
-    for (int i = 0; i < D; ++i)
-        for (int j = 0; j < D; ++j) {  // row-major tiles
-            const size_t t = 2 * (i + (size_t)j * D);
-            ps.P0[(size_t)i * D + j] = cd{P0r[t], P0r[t + 1]};
-            Br[(size_t)i * D + j] = cd{Ppr[t], Ppr[t + 1]};
-            if (i == j) {
-                ps.trP += P0r[t];
-                ps.W[i] = P0r[t];
-                // the diagonal specialisation needs P' = diag(P0' != 0) exactly
-                const double pat = P0r[t] != 0.0 ? 1.0 : 0.0;
-                if (P0r[t + 1] != 0.0 || Ppr[t + 1] != 0.0 || std::fabs(Ppr[t] - pat) > 1e-14) ps.general = true;
-            } else if (P0r[t] != 0.0 || P0r[t + 1] != 0.0 || Ppr[t] != 0.0 || Ppr[t + 1] != 0.0) {
-                ps.general = true;
-            }
-        }
-    if (ps.general) {
-        std::fill(ps.W.begin(), ps.W.end(), 0.0);
-        ps.B = Br;
-        ps.A.assign((size_t)D * D, cd{0.0, 0.0});
-        for (int i = 0; i < D; ++i)
-            for (int j = 0; j < D; ++j)
-                for (int l = 0; l < D; ++l) {
-                    const cd a = ps.P0[(size_t)i * D + l], b = Br[(size_t)l * D + j];
-                    ps.A[(size_t)i * D + j].re += a.re * b.re - a.im * b.im;
-                    ps.A[(size_t)i * D + j].im += a.re * b.im + a.im * b.re;
-                }
-    }
+    sy.ps = projector_from(P0r.data(), Ppr.data(), D);
     // worth it only when the rotated sectors are cheaper than the permutation ones
     const grape_desc rv = sy.view(desc);
     const SectorSetup rot = find_sectors(&rv, false), perm = find_sectors(desc, false);
@@ -975,15 +895,76 @@ extern "C" int grape_symmetry_basis(const grape_desc *desc, double *V, int *bloc
     return sp.rotated ? 1 : 0;
 }
 
-static int create_dense(const grape_desc *desc, grape_plan *p, bool xadd_dep, const ProjectorSetup &ps,
-                        int n_err_terms) {
-    const double trP = ps.trP;
+// the scalars of a plan's problem that come straight from the descriptor (every engine)
+static void fill_problem_scalars(const grape_desc *desc, double trP, DevProblem &P) {
+    P.D = desc->ndim;
+    P.opts = desc->reserved[1];
+    P.Nt = desc->ntimes;
+    P.np = desc->nparam;
+    P.na = desc->nadd;
+    P.ne = desc->nerr;
+    P.nx = desc->nparam * desc->ntimes + desc->nadd;
+    P.n_h0 = desc->n_h0_terms;
+    P.n_tgt = desc->n_target_terms;
+    P.dt = desc->t0 / desc->ntimes;
+    P.eps = desc->eps;
+    P.eps2 = desc->eps2;
+    P.inv_eps = 1.0 / desc->eps;
+    P.inv_eps2sq = 1.0 / (desc->eps2 * desc->eps2);
+    P.DD = trP * (trP + 1.0);
+    P.Dtr = trP;
+}
+
+// the variant list of P's scalars (grape_plan_setup.hpp build_variants) and its layout into P
+static std::vector<grape::VSpec> set_variants(DevProblem &P, int nxa, bool with_grad_variants) {
+    grape_setup::Variants V = grape_setup::build_variants(P.np, nxa, P.ne, P.eps, P.eps2, with_grad_variants);
+    P.off_dx = V.off_dx;
+    P.off_dxa = V.off_dxa;
+    P.off_dx2 = V.off_dx2;
+    P.off_err = V.off_err;
+    P.err_stride = V.err_stride;
+    return std::move(V.vs);
+}
+
+// Device copies of the term lists, the error offsets and the variant list, and their pointers in P
+// (d_err / d_err_off: plans with error sources; host-table plans upload no terms).  sfx / err_sfx name
+// the engine in the messages.
+static int upload_terms(grape_plan *p, const grape_desc *desc, int n_err_terms, const std::vector<grape::VSpec> &vs,
+                        DevProblem &P, const char *sfx, const char *err_sfx) {
+    const int ne = desc->nerr;
+    bool ok = p->mem.alloc(&p->d_h0, std::max(desc->n_h0_terms, 0)) == hipSuccess &&
+              p->mem.alloc(&p->d_tgt, std::max(desc->n_target_terms, 0)) == hipSuccess &&
+              p->mem.alloc(&p->d_vs, vs.size()) == hipSuccess;
+    if (ok && ne > 0)
+        ok = p->mem.alloc(&p->d_err, (size_t)n_err_terms) == hipSuccess &&
+             p->mem.alloc(&p->d_err_off, (size_t)ne + 1) == hipSuccess;
+    if (!ok) return fail(GRAPE_ERR_ALLOC, std::string("device allocation failed") + sfx);
+    if (hipMemcpy(p->d_vs, vs.data(), vs.size() * sizeof(grape::VSpec), hipMemcpyHostToDevice) != hipSuccess ||
+        (!p->tables &&
+         (hipMemcpy(p->d_h0, desc->h0_terms, desc->n_h0_terms * sizeof(Term), hipMemcpyHostToDevice) != hipSuccess ||
+          hipMemcpy(p->d_tgt, desc->target_terms, desc->n_target_terms * sizeof(Term), hipMemcpyHostToDevice) !=
+              hipSuccess)))
+        return fail(GRAPE_ERR_HIP, std::string("upload failed") + sfx);
+    if (ne > 0 && !p->tables &&
+        (hipMemcpy(p->d_err, desc->err_terms, n_err_terms * sizeof(Term), hipMemcpyHostToDevice) != hipSuccess ||
+         hipMemcpy(p->d_err_off, desc->err_term_offsets, ((size_t)ne + 1) * sizeof(int), hipMemcpyHostToDevice) !=
+             hipSuccess))
+        return fail(GRAPE_ERR_HIP, std::string("upload failed") + err_sfx);
+    P.h0 = p->d_h0;
+    P.tgt = p->d_tgt;
+    P.vs = p->d_vs;
+    P.err = p->d_err;
+    P.err_off = p->d_err_off;
+    return GRAPE_OK;
+}
+
+static int create_dense(const grape_desc *desc, grape_plan *p, bool xadd_dep, const ProjectorSetup &ps, int n_err_terms) {
     const int D = desc->ndim, ne = desc->nerr;
     // H0 (or Herror) reading x_add: without error sources k_dgrad adds each step's x_add variant (DP.nva);
     // with error sources (round 6) the variant table carries the x_add variants too (the small engine's
     // layout: nvg = np + na gradient parameters per step), k_dlocal / k_derr_grad write their per-step x_add
     // terms and k_dadd / k_dadd_err sum them onto the target's parts (UnitaryCalculations.jl:57-64, 87-95)
-    // Hermitian H0: checked for every engine in grape_plan_create (the dense no-interchange
+    // Hermitian H0: checked for every engine in choose_route (the dense no-interchange
     // solve relies on it too, grape_dense.hpp).  The error variants exponentiate
     // H0 + err Herror (err <= eps2): Hermitian error terms keep them inside that proof.
     for (int e = 0; e < ne; ++e)  // (each source on its own: its terms' sum must be Hermitian)
@@ -995,56 +976,12 @@ static int create_dense(const grape_desc *desc, grape_plan *p, bool xadd_dep, co
     p->dense = true;
     grape_dense::DenseProblem &DP = p->DP;
     DevProblem &P = DP.P;
-    P.D = D;
-    P.opts = desc->reserved[1];
-    P.Nt = desc->ntimes;
-    P.np = desc->nparam;
-    P.na = desc->nadd;
-    P.ne = ne;
-    P.nx = desc->nparam * desc->ntimes + desc->nadd;
-    P.n_h0 = desc->n_h0_terms;
-    P.n_tgt = desc->n_target_terms;
-    P.dt = desc->t0 / desc->ntimes;
-    P.eps = desc->eps;
-    P.eps2 = desc->eps2;
-    P.inv_eps = 1.0 / desc->eps;
-    P.inv_eps2sq = 1.0 / (desc->eps2 * desc->eps2);
-    P.DD = trP * (trP + 1.0);
-    P.Dtr = trP;
-    // propagator variants (the small engine's layout): nominal | ne > 0: dx (np) dxa (nva) | dx2 (np) dx2a (nva)
-    // | per error: err(eps), err(eps2), mixed (np), mixed x_add (nva)   UnitaryCalculations.jl:45-95
+    fill_problem_scalars(desc, ps.trP, P);
+    // propagator variants (the small engine's layout, grape_plan_setup.hpp build_variants): nominal alone
+    // without error sources (k_dgrad exponentiates its variants in place)
     const int nva = xadd_dep ? desc->nadd : 0, nvg = desc->nparam + nva;
-    std::vector<grape::VSpec> vs;
-    auto addv = [&](int var, int idx, double delta, int err, double errval) {
-        grape::VSpec v;
-        v.pert.var = var;
-        v.pert.index = idx;
-        v.pert.delta = delta;
-        v.err = err;
-        v.errval = errval;
-        vs.push_back(v);
-    };
-    addv(-1, 0, 0.0, -1, 0.0);
-    P.off_dx = (int)vs.size();
-    if (ne > 0)
-        for (int q = 0; q < P.np; ++q) addv(1, q, desc->eps, -1, 0.0);
-    P.off_dxa = (int)vs.size();
-    if (ne > 0)
-        for (int q = 0; q < nva; ++q) addv(2, q, desc->eps, -1, 0.0);
-    P.off_dx2 = (int)vs.size();
-    if (ne > 0) {
-        for (int q = 0; q < P.np; ++q) addv(1, q, desc->eps2, -1, 0.0);
-        for (int q = 0; q < nva; ++q) addv(2, q, desc->eps2, -1, 0.0);
-    }
-    P.off_err = (int)vs.size();
-    P.err_stride = 2 + nvg;
-    for (int e = 0; e < ne; ++e) {
-        addv(-1, 0, 0.0, e, desc->eps);
-        addv(-1, 0, 0.0, e, desc->eps2);
-        for (int q = 0; q < P.np; ++q) addv(1, q, desc->eps2, e, desc->eps2);
-        for (int q = 0; q < nva; ++q) addv(2, q, desc->eps2, e, desc->eps2);
-    }
-    P.nv = (int)vs.size();  // 1 without error sources (k_dgrad exponentiates its variants in place)
+    const std::vector<grape::VSpec> vs = set_variants(P, nva, ne > 0);
+    P.nv = (int)vs.size();
     P.nvg = ne > 0 ? nvg : P.np;
     DP.nz = P.nvg * (1 + ne) + ne;
     P.nz = DP.nz;
@@ -1057,37 +994,29 @@ static int create_dense(const grape_desc *desc, grape_plan *p, bool xadd_dep, co
     std::vector<double> img((size_t)desc->n_ops * IMG), W(64, 0.0);
     for (int o = 0; o < desc->n_ops; ++o) to_dense_image(desc->ops + 2 * (size_t)o * D * D, D, img.data() + o * IMG);
     for (int i = 0; i < D; ++i) W[i] = ps.W[i];
-    bool ok = dalloc(&p->dn_opimg, img.size()) == hipSuccess && dalloc(&p->dn_W, (size_t)64) == hipSuccess &&
-              dalloc(&p->d_h0, desc->n_h0_terms) == hipSuccess &&
-              dalloc(&p->d_tgt, desc->n_target_terms) == hipSuccess && dalloc(&p->d_vs, vs.size()) == hipSuccess &&
-              dalloc(&p->dn_E, MB * P.Nt * P.nv * IMG) == hipSuccess && dalloc(&p->dn_Q, MB * P.Nt * IMG) == hipSuccess &&
-              dalloc(&p->dn_Carry, MB * DP.Nc * IMG) == hipSuccess && dalloc(&p->dn_M, MB * IMG) == hipSuccess &&
-              dalloc(&p->dn_Mc, MB * DP.Nc * IMG) == hipSuccess &&
-              dalloc(&p->dn_Z, ne ? 1 : MB * P.Nt * IMG) == hipSuccess &&
-              dalloc(&p->d_x, MB * P.nx) == hipSuccess &&
-              dalloc(&p->d_F, MB) == hipSuccess && dalloc(&p->d_Fdx, MB * P.nx) == hipSuccess &&
-              dalloc(&p->d_ctrl, kCtrlInts) == hipSuccess;
-    if (ok && DP.nva > 0) ok = dalloc(&p->dn_Fadd, MB * P.Nt * DP.nva) == hipSuccess;
-    if (ok && DP.nva > 0 && ne > 0) ok = dalloc(&p->dn_Fd2add, MB * NE * P.Nt * DP.nva) == hipSuccess;
+    bool ok = p->mem.alloc(&p->dn_opimg, img.size()) == hipSuccess && p->mem.alloc(&p->dn_W, (size_t)64) == hipSuccess &&
+              p->mem.alloc(&p->dn_E, MB * P.Nt * P.nv * IMG) == hipSuccess && p->mem.alloc(&p->dn_Q, MB * P.Nt * IMG) == hipSuccess &&
+              p->mem.alloc(&p->dn_Carry, MB * DP.Nc * IMG) == hipSuccess && p->mem.alloc(&p->dn_M, MB * IMG) == hipSuccess &&
+              p->mem.alloc(&p->dn_Mc, MB * DP.Nc * IMG) == hipSuccess &&
+              p->mem.alloc(&p->dn_Z, ne ? 1 : MB * P.Nt * IMG) == hipSuccess &&
+              p->mem.alloc(&p->d_x, MB * P.nx) == hipSuccess &&
+              p->mem.alloc(&p->d_F, MB) == hipSuccess && p->mem.alloc(&p->d_Fdx, MB * P.nx) == hipSuccess &&
+              p->mem.alloc(&p->d_ctrl, kCtrlInts) == hipSuccess;
+    if (ok && DP.nva > 0) ok = p->mem.alloc(&p->dn_Fadd, MB * P.Nt * DP.nva) == hipSuccess;
+    if (ok && DP.nva > 0 && ne > 0) ok = p->mem.alloc(&p->dn_Fd2add, MB * NE * P.Nt * DP.nva) == hipSuccess;
     if (ok && ne > 0)
-        ok = dalloc(&p->dn_Ub, MB * IMG) == hipSuccess && dalloc(&p->dn_Zl, MB * P.Nt * DP.nz * IMG) == hipSuccess &&
-             dalloc(&p->dn_Vc, MB * NE * DP.Nc * IMG) == hipSuccess &&
-             dalloc(&p->dn_Sx, MB * NE * DP.Nc * IMG) == hipSuccess && dalloc(&p->dn_Tot, MB * NE * IMG) == hipSuccess &&
-             dalloc(&p->dn_Me, MB * NE * IMG) == hipSuccess && dalloc(&p->dn_Mp, MB * NE * DP.Nc * IMG) == hipSuccess &&
-             dalloc(&p->dn_B0, MB * NE * DP.Nc * IMG) == hipSuccess && dalloc(&p->d_Fd2, MB * NE) == hipSuccess &&
-             dalloc(&p->d_Fd2dx, MB * NE * P.nx) == hipSuccess && dalloc(&p->d_err, (size_t)n_err_terms) == hipSuccess &&
-             dalloc(&p->d_err_off, NE + 1) == hipSuccess;
-    if (ok && ps.general && ne == 0) ok = dalloc(&p->dn_Ub, MB * IMG) == hipSuccess;
+        ok = p->mem.alloc(&p->dn_Ub, MB * IMG) == hipSuccess && p->mem.alloc(&p->dn_Zl, MB * P.Nt * DP.nz * IMG) == hipSuccess &&
+             p->mem.alloc(&p->dn_Vc, MB * NE * DP.Nc * IMG) == hipSuccess &&
+             p->mem.alloc(&p->dn_Sx, MB * NE * DP.Nc * IMG) == hipSuccess && p->mem.alloc(&p->dn_Tot, MB * NE * IMG) == hipSuccess &&
+             p->mem.alloc(&p->dn_Me, MB * NE * IMG) == hipSuccess && p->mem.alloc(&p->dn_Mp, MB * NE * DP.Nc * IMG) == hipSuccess &&
+             p->mem.alloc(&p->dn_B0, MB * NE * DP.Nc * IMG) == hipSuccess && p->mem.alloc(&p->d_Fd2, MB * NE) == hipSuccess &&
+             p->mem.alloc(&p->d_Fd2dx, MB * NE * P.nx) == hipSuccess;
+    if (ok && ps.general && ne == 0) ok = p->mem.alloc(&p->dn_Ub, MB * IMG) == hipSuccess;
     if (!ok) return fail(GRAPE_ERR_ALLOC, "device allocation failed (dense)");
     {  // row-major operator basis: the general-projector heads and the analysis kernels
         std::vector<cd> ops((size_t)desc->n_ops * D * D);
-        for (int o = 0; o < desc->n_ops; ++o)
-            for (int r = 0; r < D; ++r)
-                for (int c = 0; c < D; ++c) {
-                    const double *src = desc->ops + 2 * ((size_t)o * D * D + r + (size_t)c * D);
-                    ops[(size_t)o * D * D + r * D + c] = cd{src[0], src[1]};
-                }
-        if (dalloc(&p->d_ops, ops.size()) != hipSuccess ||
+        grape_setup::to_tiles(desc->ops, desc->n_ops, D, nullptr, 1, D, ops.data(), nullptr);
+        if (p->mem.alloc(&p->d_ops, ops.size()) != hipSuccess ||
             hipMemcpy(p->d_ops, ops.data(), ops.size() * sizeof(cd), hipMemcpyHostToDevice) != hipSuccess)
             return fail(GRAPE_ERR_ALLOC, "device allocation failed (dense, general projector)");
         P.ops = p->d_ops;
@@ -1095,26 +1024,591 @@ static int create_dense(const grape_desc *desc, grape_plan *p, bool xadd_dep, co
     if (int rc = upload_projector(p, ps, P, MB * std::max<size_t>(NE, 1))) return rc;
     if (hipMemset(p->d_ctrl, 0, kCtrlInts * sizeof(int)) != hipSuccess ||
         hipMemcpy(p->dn_opimg, img.data(), img.size() * sizeof(double), hipMemcpyHostToDevice) != hipSuccess ||
-        hipMemcpy(p->dn_W, W.data(), 64 * sizeof(double), hipMemcpyHostToDevice) != hipSuccess ||
-        hipMemcpy(p->d_vs, vs.data(), vs.size() * sizeof(grape::VSpec), hipMemcpyHostToDevice) != hipSuccess ||
-        hipMemcpy(p->d_h0, desc->h0_terms, desc->n_h0_terms * sizeof(Term), hipMemcpyHostToDevice) != hipSuccess ||
-        hipMemcpy(p->d_tgt, desc->target_terms, desc->n_target_terms * sizeof(Term), hipMemcpyHostToDevice) !=
-            hipSuccess)
+        hipMemcpy(p->dn_W, W.data(), 64 * sizeof(double), hipMemcpyHostToDevice) != hipSuccess)
         return fail(GRAPE_ERR_HIP, "upload failed (dense)");
-    if (ne > 0 &&
-        (hipMemcpy(p->d_err, desc->err_terms, n_err_terms * sizeof(Term), hipMemcpyHostToDevice) != hipSuccess ||
-         hipMemcpy(p->d_err_off, desc->err_term_offsets, (NE + 1) * sizeof(int), hipMemcpyHostToDevice) != hipSuccess))
-        return fail(GRAPE_ERR_HIP, "upload failed (dense error terms)");
-    P.h0 = p->d_h0;
-    P.tgt = p->d_tgt;
-    P.vs = p->d_vs;
-    P.err = p->d_err;
-    P.err_off = p->d_err_off;
+    if (int rc = upload_terms(p, desc, n_err_terms, vs, P, " (dense)", " (dense error terms)")) return rc;
     DP.opimg = p->dn_opimg;
     DP.W = p->dn_W;
     P.W = p->dn_W;  // zero-padded to 64; the analysis kernels (expectation values) read W[0..D)
     p->P = P;  // the C ABI reads nx / np / ne from the plan's problem for every engine
     return GRAPE_OK;
+}
+
+// ---------------------------------------------------------------------------
+// plan creation, phase by phase (grape_plan_create calls them top to bottom; each returns a GRAPE_*
+// code with the message set, and the caller frees the plan on any failure)
+// ---------------------------------------------------------------------------
+// Everything checkable without a device, in this order (a machine without one sees these codes
+// before GRAPE_ERR_NO_DEVICE).
+static int validate_desc(const grape_desc *desc, int *n_err_terms) {
+    const int D = desc->ndim;
+    const bool tables = (desc->reserved[0] & GRAPE_DESC_HOST_TABLES) != 0;
+    if (D < 2 || desc->ntimes < 1 || desc->nparam < 1 || desc->nadd < 0 || desc->nerr < 0 ||
+        (!tables && desc->n_ops < 1))
+        return fail(GRAPE_ERR_INVALID, "bad dimensions in descriptor");
+    if (D > GRAPE_MAX_DENSE_DIM) return fail(GRAPE_ERR_UNSUPPORTED, "ndim > GRAPE_MAX_DENSE_DIM");
+    if (tables) {  // above GRAPE_MAX_SMALL_DIM: the general path with the dense exponential of the tables
+        if (!desc->projector_diag && !desc->projector) return fail(GRAPE_ERR_INVALID, "missing projector");
+    } else {
+        if (desc->nerr > 0 && !desc->err_term_offsets) return fail(GRAPE_ERR_INVALID, "missing err_term_offsets");
+        if (!desc->ops || !desc->h0_terms || desc->n_h0_terms < 1 || (!desc->projector_diag && !desc->projector) ||
+            !desc->target_terms || desc->n_target_terms < 1)
+            return fail(GRAPE_ERR_INVALID, "missing operator basis / terms / projector");
+    }
+    if (!(desc->t0 > 0) || !(desc->eps > 0)) return fail(GRAPE_ERR_INVALID, "t0 and eps must be positive");
+    int rc;
+    if (!tables && (rc = validate_terms(desc->h0_terms, desc->n_h0_terms, desc->n_ops, desc->nparam, desc->nadd, false, "H0")))
+        return rc;
+    if (!tables && (rc = validate_terms(desc->target_terms, desc->n_target_terms, desc->n_ops, desc->nparam, desc->nadd, true,
+                             "target")))
+        return rc;
+    *n_err_terms = 0;
+    if (desc->nerr > 0 && !tables) {
+        for (int e = 0; e < desc->nerr; ++e)
+            if (desc->err_term_offsets[e + 1] <= desc->err_term_offsets[e])
+                return fail(GRAPE_ERR_INVALID, "each error source needs at least one term");
+        if (desc->err_term_offsets[0] != 0) return fail(GRAPE_ERR_INVALID, "err_term_offsets[0] must be 0");
+        *n_err_terms = desc->err_term_offsets[desc->nerr];
+        if ((rc = validate_terms(desc->err_terms, *n_err_terms, desc->n_ops, desc->nparam, desc->nadd, false,
+                                 "error source")))
+            return rc;
+    }
+    return GRAPE_OK;
+}
+
+// Which engine serves the descriptor (pure host logic).
+struct Route {
+    bool tables = false;      // GRAPE_DESC_HOST_TABLES: host-evaluated H and target tables
+    bool general_h0 = false;  // the general path (materialised derivatives, LU inverse of the chain)
+    bool pivot = false;       // ... over the dense engine's pivoted exponential (12 < d <= 64)
+    bool xadd_dep = false;    // H0 or an error source reads x_add: x_add variants exist
+    bool err_herm = true;     // Hermitian error generators
+};
+static int choose_route(const grape_desc *desc, int n_err_terms, Route &rt) {
+    const int D = desc->ndim;
+    rt.tables = (desc->reserved[0] & GRAPE_DESC_HOST_TABLES) != 0;
+    rt.general_h0 = (desc->reserved[1] & GRAPE_OPT_GENERAL_H0) != 0;
+    if (!rt.tables && !rt.general_h0)
+        if (int rc = check_hermitian_terms(desc, desc->h0_terms, desc->n_h0_terms, "H0")) {
+            if (rc != GRAPE_ERR_UNSUPPORTED || D > GRAPE_MAX_SMALL_DIM) return rc;
+            rt.general_h0 = true;  // non-Hermitian H0: the general path serves it
+        }
+    // 12 < d <= 64 with the option: the general path over the dense engine's pivoted exponential
+    // (operator bases: setup_pivot_dense, after the general-path problem; host tables:
+    // launch_table_variants).  Without the option nothing changes: a non-Hermitian H0 or error source
+    // is refused above.
+    rt.pivot = rt.general_h0 && D > GRAPE_MAX_SMALL_DIM;
+    // closures above the small engine: host tables through the general path (materialised
+    // derivatives), each tabulated generator exponentiated by the dense engine (grape_dense.hip
+    // launch_table_variants; the host checks that the tables are Hermitian)
+    if (rt.tables && D > GRAPE_MAX_SMALL_DIM) rt.general_h0 = true;
+    // host tables: H0 / Herror are opaque closures that may read x_add, so every x_add call
+    // site of the reference is tabulated (UnitaryCalculations.jl:57-64, 87-95)
+    rt.xadd_dep = rt.tables && desc->nadd > 0;
+    for (int k = 0; k < (rt.tables ? 0 : desc->n_h0_terms); ++k)
+        if (desc->h0_terms[k].var == 2) rt.xadd_dep = true;
+    for (int k = 0; k < n_err_terms; ++k)
+        if (desc->err_terms[k].var == 2) rt.xadd_dep = true;
+    // Hermitian error generators (the image walk's exponential is skew-Hermitian, grape_walk.hpp)
+    rt.err_herm = rt.tables || hermitian_terms(desc, desc->err_terms, n_err_terms) == 0;
+    return GRAPE_OK;
+}
+
+// the plan's device, stream and pinned status word
+static int open_plan(grape_plan *p, const grape_desc *desc, int device, const Route &rt) {
+    for (int k = 0; k < (rt.tables ? 0 : desc->n_h0_terms); ++k)
+        if (desc->h0_terms[k].var == GRAPE_VAR_TSTEP) p->uses_tstep = true;
+    p->device = device;
+    p->max_batch = desc->max_batch > 0 ? desc->max_batch : 256;
+    p->pivot = rt.pivot;
+    if (hipSetDevice(device) != hipSuccess) return fail(GRAPE_ERR_HIP, "hipSetDevice failed");
+    if (hipStreamCreateWithFlags(&p->own_stream, hipStreamNonBlocking) != hipSuccess)
+        return fail(GRAPE_ERR_HIP, "hipStreamCreate failed");
+    p->stream = p->own_stream;
+    if (hipHostMalloc(reinterpret_cast<void **>(&p->h_status), sizeof(int), hipHostMallocDefault) != hipSuccess)
+        return fail(GRAPE_ERR_ALLOC, "pinned allocation failed");
+    *p->h_status = 0;
+    return GRAPE_OK;
+}
+
+// What the phases of a small-engine / general-path plan share.
+struct PlanBuild {
+    const grape_desc *desc;
+    grape_plan *p;
+    const Route &rt;
+    const ProjectorSetup &ps;
+    int n_err_terms;
+    int ncu = 256;          // compute units of the plan's device
+    int scan_override = 0;  // plan option: 1, 4, 8 or 16 waves (0: by batch size)
+    int n_ops = 0;
+    std::vector<grape::VSpec> vs;
+    // the sector path's view: rotated operators and projector when the symmetry-adapted sectors are on
+    SymSetup sym;
+    grape_desc sdesc{};
+    SectorSetup ss;
+    const ProjectorSetup &sps() const { return sym.on ? sym.ps : ps; }
+};
+
+// The whole-matrix problem P: scalars, variant layout, scan chunking; then the sector layout (host).
+static int setup_problem(PlanBuild &b) {
+    const grape_desc *desc = b.desc;
+    grape_plan *p = b.p;
+    const int D = desc->ndim;
+    if (D <= GRAPE_MAX_SMALL_DIM && dispatch_lds_limits(D) != hipSuccess)
+        return fail(GRAPE_ERR_HIP, "cannot raise LDS limit");
+    DevProblem &P = p->P;
+    p->tables = b.rt.tables;
+    p->general_h0 = b.rt.general_h0;
+    b.n_ops = b.rt.tables ? 0 : desc->n_ops;
+    fill_problem_scalars(desc, b.ps.trP, P);
+    P.xadd_dep = b.rt.xadd_dep ? 1 : 0;
+    // propagator variants of one step (grape_plan_setup.hpp build_variants), with the x_add variants
+    // only if H0 reads x_add
+    const int nad = b.rt.xadd_dep ? desc->nadd : 0;
+    b.vs = set_variants(P, nad, true);
+    // E stores every variant for the error-source pipeline; without error sources
+    // only the nominal propagators are stored (k_expm_grad consumes the rest in place)
+    // host tables: every variant's propagator is stored (k_grad reads them back)
+    P.nv = (desc->nerr > 0 || b.rt.tables) ? (int)b.vs.size() : 1;
+    P.nvg = desc->nparam + nad;
+    P.nz = P.nvg * (1 + desc->nerr) + desc->nerr;
+    // scan width: narrow once a launch can hold two evaluations per CU
+    hipDeviceProp_t prop;
+    if (hipGetDeviceProperties(&prop, p->device) == hipSuccess && prop.multiProcessorCount > 0)
+        b.ncu = prop.multiProcessorCount;
+    b.scan_override = desc->reserved[2];
+    P.scan_waves = p->max_batch >= 2 * b.ncu ? kScanNarrow : kScanWide;
+    if (b.scan_override == kScanNarrow || b.scan_override == kScanWide) P.scan_waves = b.scan_override;
+    const int nc0 = std::min(P.scan_waves * (64 / D), P.Nt);
+    P.L = (P.Nt + nc0 - 1) / nc0;
+    P.nchunks = (P.Nt + P.L - 1) / P.L;
+    P.sectors = 0;
+    P.nsec = 1;
+    P.sec_ops = 0;
+    // symmetry-adapted sectors: the sector path (operators, head) in the rotated basis when that
+    // splits the sectors further; the whole-matrix problem P keeps the caller's basis
+    if (!b.rt.general_h0 && !b.rt.tables) b.sym = symmetry_setup(desc);
+    b.sdesc = b.sym.on ? b.sym.view(desc) : *desc;
+    if (!b.rt.general_h0) b.ss = find_sectors(&b.sdesc, b.rt.tables);
+    p->symmetry = b.sym.on;
+    return GRAPE_OK;
+}
+
+// The whole-matrix workspace (no rows when sectors or the general-H0 path run), the per-call buffers
+// every path uses, and the uploads of operators, terms, weights and projector.
+static int alloc_whole_matrix(PlanBuild &b) {
+    const grape_desc *desc = b.desc;
+    grape_plan *p = b.p;
+    DevProblem &P = p->P;
+    const bool tables = b.rt.tables;
+    const int D = P.D;
+    const size_t FR = (!b.ss.cls.empty() || b.rt.general_h0) ? 0 : (size_t)p->max_batch;
+    const size_t MB = p->max_batch, T = (size_t)D * D;
+    std::vector<cd> ops((size_t)b.n_ops * T), opsT(ops.size());
+    grape_setup::to_tiles(desc->ops, b.n_ops, D, nullptr, 1, D, ops.data(), opsT.data());
+    bool ok = p->mem.alloc(&p->d_ops, ops.size()) == hipSuccess && p->mem.alloc(&p->d_opsT, opsT.size()) == hipSuccess &&
+              p->mem.alloc(&p->d_W, (size_t)D) == hipSuccess &&
+              p->mem.alloc(&p->d_E, FR * P.Nt * P.nv * T) == hipSuccess && p->mem.alloc(&p->d_Q, FR * P.Nt * T) == hipSuccess &&
+              p->mem.alloc(&p->d_Mc, FR * P.nchunks * T) == hipSuccess && p->mem.alloc(&p->d_x, MB * P.nx) == hipSuccess &&
+              p->mem.alloc(&p->d_F, MB) == hipSuccess && p->mem.alloc(&p->d_Fdx, MB * P.nx) == hipSuccess &&
+              p->mem.alloc(&p->d_part, MB * P.Nt * std::max(P.na, 1)) == hipSuccess &&
+              p->mem.alloc(&p->d_tgt_part, MB * std::max(P.na, 1)) == hipSuccess &&
+              p->mem.alloc(&p->d_ovf, FR * P.Nt * P.nv) == hipSuccess && p->mem.alloc(&p->d_ctrl, kCtrlInts) == hipSuccess &&
+              p->mem.alloc(&p->d_sink, T) == hipSuccess;
+    if (ok && P.ne == 0)
+        ok = p->mem.alloc(&p->d_ovf2, FR * P.Nt * P.nvg) == hipSuccess &&
+             p->mem.alloc(&p->d_ovf2_slots, FR * P.Nt * P.nvg * T) == hipSuccess;
+    if (ok && (P.ne > 0 || b.ps.general))  // carries and U: the error path and the general-projector heads
+        ok = p->mem.alloc(&p->d_Carry, FR * P.nchunks * T) == hipSuccess && p->mem.alloc(&p->d_Ub, FR * T) == hipSuccess;
+    if (ok && P.ne > 0)
+        ok = p->mem.alloc(&p->d_Me, FR * P.ne * P.nchunks * 3 * T) == hipSuccess &&
+             p->mem.alloc(&p->d_Fd2, MB * P.ne) == hipSuccess && p->mem.alloc(&p->d_Fd2dx, MB * P.ne * P.nx) == hipSuccess &&
+             p->mem.alloc(&p->d_Zl, FR * P.Nt * P.nz * T) == hipSuccess;
+    if (ok && P.ne > 0 && P.xadd_dep)
+        ok = p->mem.alloc(&p->d_part_err, MB * P.ne * P.Nt * P.na) == hipSuccess;
+    if (ok && tables)
+        ok = p->mem.alloc(&p->d_Htab, MB * P.Nt * P.nv * T) == hipSuccess &&
+             p->mem.alloc(&p->d_U0tab, MB * (1 + P.na) * T) == hipSuccess;
+    if (!ok) return fail(GRAPE_ERR_ALLOC, "device allocation failed");
+    if (hipMemset(p->d_ctrl, 0, kCtrlInts * sizeof(int)) != hipSuccess) return fail(GRAPE_ERR_HIP, "memset failed");
+    if (int rc = upload_terms(p, desc, b.n_err_terms, b.vs, P, "", "")) return rc;
+    if ((!tables &&
+         (hipMemcpy(p->d_ops, ops.data(), ops.size() * sizeof(cd), hipMemcpyHostToDevice) != hipSuccess ||
+          hipMemcpy(p->d_opsT, opsT.data(), opsT.size() * sizeof(cd), hipMemcpyHostToDevice) != hipSuccess)) ||
+        hipMemcpy(p->d_W, b.ps.W.data(), D * sizeof(double), hipMemcpyHostToDevice) != hipSuccess)
+        return fail(GRAPE_ERR_HIP, "upload failed");
+    if (int rc = upload_projector(p, b.ps, P, MB * std::max(P.ne, 1))) return rc;
+    P.ops = p->d_ops;
+    P.opsT = p->d_opsT;
+    P.W = p->d_W;
+    return GRAPE_OK;
+}
+
+// a diagonal projector's tiles A = diag(w), B = diag(w != 0) (or the given general ones) on the device
+static hipError_t upload_projector_tiles(grape_plan *p, const std::vector<cd> &A, const std::vector<cd> &B, cd **dA, cd **dB) {
+    hipError_t e = p->mem.alloc(dA, A.size());
+    if (e == hipSuccess) e = p->mem.alloc(dB, B.size());
+    if (e == hipSuccess) e = hipMemcpy(*dA, A.data(), A.size() * sizeof(cd), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(*dB, B.data(), B.size() * sizeof(cd), hipMemcpyHostToDevice);
+    return e;
+}
+
+// General H0: the fidelity heads need P0 P and P as tiles; the chain's inverses and the head's scratch.
+static int setup_general_h0(PlanBuild &b) {
+    if (!b.rt.general_h0) return GRAPE_OK;
+    grape_plan *p = b.p;
+    DevProblem &P = p->P;
+    const size_t T = (size_t)P.D * P.D;
+    if (!b.ps.general) {
+        std::vector<cd> A, Bm;
+        grape_setup::diag_projector_tiles(b.ps.W.data(), P.D, A, Bm);
+        if (upload_projector_tiles(p, A, Bm, &p->d_PA, &p->d_PB) != hipSuccess)
+            return fail(GRAPE_ERR_ALLOC, "device allocation failed (general H0)");
+        P.PA = p->d_PA;
+        P.PB = p->d_PB;
+    }
+    if (p->mem.alloc(&p->ud_Ci, (size_t)P.Nt * T) != hipSuccess || p->mem.alloc(&p->d_G, (1 + (size_t)P.ne) * T) != hipSuccess ||
+        (P.D > grape_unitary::kMaxD && p->mem.alloc(&p->d_fscr, (size_t)grape_unitary::kFidTiles * T) != hipSuccess))
+        return fail(GRAPE_ERR_ALLOC, "device allocation failed (general H0)");
+    return GRAPE_OK;
+}
+
+// The head over the assembled U (SH): its projector tiles, weights and operators (the rotated ones
+// with symmetry-adapted sectors), the fixed levels, and the choice of the diagonal head.
+static int setup_sector_head(PlanBuild &b) {
+    const grape_desc *desc = b.desc;
+    grape_plan *p = b.p;
+    const DevProblem &P = p->P;
+    const ProjectorSetup &sps = b.sps();
+    const SectorSetup &ss = b.ss;
+    const bool sym = b.sym.on;
+    const int D = P.D;
+    std::vector<cd> A, Bm;
+    grape_setup::diag_projector_tiles(sps.W.data(), D, A, Bm);
+    if (sym && sps.general) {
+        A = sps.A;
+        Bm = sps.B;
+    }
+    if (sym) {  // the head's own rotated projector tiles, weights and operators
+        std::vector<cd> rops((size_t)b.n_ops * D * D), ropsT(rops.size());
+        grape_setup::to_tiles(b.sym.ops.data(), b.n_ops, D, nullptr, 1, D, rops.data(), ropsT.data());
+        if (upload_projector_tiles(p, A, Bm, &p->d_PA_sym, &p->d_PB_sym) != hipSuccess ||
+            p->mem.alloc(&p->d_W_sym, (size_t)D) != hipSuccess || p->mem.alloc(&p->d_ops_sym, rops.size()) != hipSuccess ||
+            p->mem.alloc(&p->d_opsT_sym, ropsT.size()) != hipSuccess ||
+            hipMemcpy(p->d_W_sym, sps.W.data(), D * sizeof(double), hipMemcpyHostToDevice) != hipSuccess ||
+            hipMemcpy(p->d_ops_sym, rops.data(), rops.size() * sizeof(cd), hipMemcpyHostToDevice) != hipSuccess ||
+            hipMemcpy(p->d_opsT_sym, ropsT.data(), ropsT.size() * sizeof(cd), hipMemcpyHostToDevice) != hipSuccess)
+            return fail(GRAPE_ERR_ALLOC, "device allocation failed (symmetry sectors)");
+    } else if (!b.ps.general && upload_projector_tiles(p, A, Bm, &p->d_PA, &p->d_PB) != hipSuccess) {
+        return fail(GRAPE_ERR_ALLOC, "device allocation failed (sectors)");
+    }
+    if (p->mem.alloc(&p->d_fixed, ss.fixed.size()) != hipSuccess ||
+        (!ss.fixed.empty() && hipMemcpy(p->d_fixed, ss.fixed.data(), ss.fixed.size() * sizeof(int),
+                                        hipMemcpyHostToDevice) != hipSuccess))
+        return fail(GRAPE_ERR_ALLOC, "device allocation failed (sectors)");
+    grape_proj::SectorHead &H = p->SH;
+    H.P = P;
+    H.P.PA = sym ? p->d_PA_sym : p->d_PA;
+    H.P.PB = sym ? p->d_PB_sym : p->d_PB;
+    if (sym) {
+        H.P.W = p->d_W_sym;
+        H.P.ops = p->d_ops_sym;
+        H.P.opsT = p->d_opsT_sym;
+    }
+    H.ncls = (int)ss.cls.size();
+    H.fixed = p->d_fixed;
+    H.nfixed = (int)ss.fixed.size();
+    // diagonal projector and target, classes of <= 4 levels: the one-thread-per-evaluation head
+    // (grape_projector.hip k_sec_head_diag)
+    H.diag = !sps.general && !b.rt.tables && !(P.opts & GRAPE_OPT_GENERAL_HEAD);
+    int rows = 0;  // the row-parallel head's lanes per evaluation (grape_projector.hip diag_group)
+    for (const SectorClass &sc : ss.cls) {
+        H.diag = H.diag && sc.S <= 4;
+        rows += sc.nsec * sc.S;
+    }
+    H.diag = H.diag && rows <= 32;
+    for (int k = 0; H.diag && k < desc->n_target_terms; ++k) {
+        const double *op = b.sdesc.ops + 2 * (size_t)desc->target_terms[k].op * D * D;
+        for (int i = 0; i < D; ++i)
+            for (int j = 0; j < D; ++j)
+                if (i != j && (op[2 * (i + (size_t)j * D)] != 0.0 || op[2 * (i + (size_t)j * D) + 1] != 0.0))
+                    H.diag = 0;
+    }
+    return GRAPE_OK;
+}
+
+// Every decision about one sector class, into Ps (pure host logic; gauge_n: the class's charges, for
+// alloc_class to upload; sops: the class's operator tiles [w][o][S][S]).
+static void decide_class(const PlanBuild &b, const SectorClass &sc, const std::vector<cd> &sops, DevProblem &Ps,
+                         std::vector<int> &gauge_n) {
+    const grape_desc *desc = b.desc;
+    const DevProblem &P = b.p->P;
+    const int S = sc.S, ncu = b.ncu, scan_override = b.scan_override;
+    const size_t TS = (size_t)S * S, MB = b.p->max_batch, R = MB * sc.nsec;  // workspace rows: sub-evaluations
+    Ps = P;
+    Ps.D = S;
+    Ps.sectors = 1;
+    Ps.nsec = sc.nsec;
+    Ps.sec_ops = (size_t)b.n_ops * TS;
+    Ps.gen_proj = 0;
+    Ps.scan_waves = (long)R >= 8L * ncu ? kScanTiny : (long)R >= 2L * ncu ? kScanNarrow : kScanWide;
+    if (scan_override == kScanTiny || scan_override == kScanNarrow || scan_override == kScanWide)
+        Ps.scan_waves = scan_override;
+    // chunk walks (grape_walk.hpp): classes of <= kWalkMaxD levels; with error sources the
+    // image walk (k_walk_img), for any number of gradient parameters per step
+    // (its exponential keeps A skew-Hermitian in compressed form: Hermitian error generators only;
+    // a decay-rate error, -i e/2 |r><r|, keeps the stored-variant kernels)
+    Ps.walk = (S <= grape::kWalkMaxD && (P.ne == 0 || b.rt.err_herm) && P.np <= grape::kWalkMaxNpA &&
+               P.na <= grape::kWalkMaxNpA && !(P.opts & GRAPE_OPT_NO_WALK)) ? 1 : 0;
+    // phase-covariant classes (grape_walk.hpp GAUGE): one exponential per walk lane
+    // (with error sources: the phase-covariant image walk, one gradient parameter per step)
+    double gauge_a = 1.0;
+    Ps.gauge = (Ps.walk && (P.ne == 0 || (P.nvg == 1 && P.ne <= grape::kGaugeMaxE)) &&
+                !(P.opts & GRAPE_OPT_NO_GAUGE) && find_gauge(desc, b.sdesc, sc, gauge_a, gauge_n)) ? 1 : 0;
+    Ps.gauge_a = gauge_a;
+    Ps.gauge_n = nullptr;
+    Ps.gauge_ladder = Ps.gauge;
+    for (size_t i = 0; Ps.gauge && i < gauge_n.size(); ++i)
+        if (gauge_n[i] != (int)(i % (size_t)S)) Ps.gauge_ladder = 0;
+    // error sources on a phase-covariant class: the lab-frame walks (no images, grape_walk.hpp
+    // GRAPE_WALK_ERR_LAB) when the base table's lanes fit one workgroup
+    Ps.gauge_lab = (GRAPE_WALK_ERR_LAB && Ps.gauge && P.ne > 0 &&
+                    sc.nsec * (1 + 2 * P.ne) <= grape::kLabBaseMaxLanes) ? 1 : 0;
+    Ps.gauge_Et = nullptr;
+    // the forward walk hands its propagators to the gradient walk (HBM, lane-minor) where the
+    // exponential is the expensive part: the 4-level class (grape_walk.hpp; measured C2 6.04 ->
+    // 6.52 M evals/s; for the 2-level class it lost, 0.72 -> 1.01 ms per pass)
+    Ps.walk_store_e = Ps.walk && !Ps.gauge && P.ne == 0 && S >= grape::kWalkStoreMinD &&
+                      !(P.opts & GRAPE_OPT_WALK_RECOMPUTE) ? 1 : 0;
+    // latency-bound walk classes (fewer sub-evaluations than CUs, or the option): 16-wave scans,
+    // half-length walks (grape_launch.hpp kScanLatency)
+    // (GRAPE_LAB_LATENCY_SCAN: the lab-frame error walks too)
+    if (Ps.walk && (P.ne == 0 || (Ps.gauge_lab && GRAPE_LAB_LATENCY_SCAN)) &&
+        (scan_override == kScanLatency || (scan_override == 0 && (long)R < (long)ncu)))
+        Ps.scan_waves = kScanLatency;
+    // phase-covariant throughput classes: a step costs a few products instead of an
+    // exponential, so longer chunks (fewer per-lane prologues and a shorter scan) can pay
+    const int cdiv = (Ps.gauge && Ps.scan_waves == kScanTiny) ? (S == 2 ? GRAPE_GAUGE_CHUNK_DIV2 : GRAPE_GAUGE_CHUNK_DIV) : 1;
+    int ncs = std::max(1, std::min(Ps.scan_waves * (64 / S) / cdiv, P.Nt));
+    if (Ps.gauge && Ps.scan_waves == kScanTiny && S == 3 && P.ne == 0)
+        ncs = merged_chunk_count((long)MB, P.Nt, ncs, ncu);
+    // the lab-frame error walks' throughput chunking (A/B knobs; 0: the formula above)
+    if (Ps.gauge_lab && Ps.scan_waves == kScanTiny) {
+        const int lc = S >= 4 ? GRAPE_LAB_CHUNKS4 : GRAPE_LAB_CHUNKS2;
+        if (lc > 0) ncs = std::max(1, std::min(lc, P.Nt));
+    }
+    Ps.L = (P.Nt + ncs - 1) / ncs;
+    Ps.nchunks = (P.Nt + Ps.L - 1) / Ps.L;
+    // twin sectors (grape_walk.hpp TWIN): two walk sectors whose blocks of every operator H0
+    // and the error sources use are identical, with the same padding -- one exponential
+    // per step serves both (the 2-level Rydberg sectors at equal Rabi frequencies)
+    Ps.twin = 0;
+    // (S == 2 only: launch<2> is the one launcher that runs a class with two sectors per lane)
+    if (Ps.walk && P.ne == 0 && sc.nsec == 2 && S == 2 && !Ps.walk_store_e && !(P.opts & GRAPE_OPT_NO_TWIN)) {
+        bool same = true;
+        for (int a = 0; a < S; ++a) same = same && ((sc.sidx[a] < 0) == (sc.sidx[S + a] < 0));
+        std::vector<char> used(b.n_ops, 0);
+        for (int t = 0; t < desc->n_h0_terms; ++t) used[desc->h0_terms[t].op] = 1;
+        for (int o = 0; same && o < b.n_ops; ++o)
+            if (used[o])
+                same = std::memcmp(&sops[(size_t)o * TS], &sops[((size_t)b.n_ops + o) * TS], TS * sizeof(cd)) == 0;
+        Ps.twin = same ? 1 : 0;
+    }
+}
+
+// The workspace of one sector class (sb[cl]) as decide_class sized it, and the uploads of its
+// charges, operator tiles and level indices.
+static int alloc_class(PlanBuild &b, int cl, const std::vector<int> &gauge_n, const std::vector<cd> &sops,
+                       const std::vector<cd> &sopsT) {
+    grape_plan *p = b.p;
+    const DevProblem &P = p->P;
+    DevProblem &Ps = p->Ps[cl];
+    const SectorClass &sc = b.ss.cls[cl];
+    grape_plan::SecBuf &sb = p->sb[cl];
+    const size_t TS = (size_t)sc.S * sc.S, MB = p->max_batch, R = MB * sc.nsec, nvg = P.nvg;
+    if (Ps.gauge) {
+        if (p->mem.alloc(&sb.gauge_n, gauge_n.size()) != hipSuccess) return fail(GRAPE_ERR_ALLOC, "device allocation failed (gauge)");
+        if (hipMemcpy(sb.gauge_n, gauge_n.data(), gauge_n.size() * sizeof(int), hipMemcpyHostToDevice) != hipSuccess)
+            return fail(GRAPE_ERR_HIP, "upload failed (gauge)");
+        Ps.gauge_n = sb.gauge_n;
+    }
+    const size_t ne = (size_t)P.ne, R2 = (P.ne > 0 || Ps.walk) ? 0 : R;  // k_expm_grad parking: no error sources only
+    const size_t RE = Ps.walk ? 0 : R;  // the walks store no E / Q
+    const size_t lanes_pad = (MB * Ps.nchunks + grape::kWalkBlockA - 1) / grape::kWalkBlockA * grape::kWalkBlockA;
+    // stored propagators: D*D elements + the diagonal shift per (step, sector) (grape_walk.hpp kEwStride)
+    if (Ps.walk_store_e && p->mem.alloc(&sb.Ew, (size_t)sc.nsec * Ps.L * (TS + 1) * lanes_pad) != hipSuccess)
+        return fail(GRAPE_ERR_ALLOC, "device allocation failed (sector walks)");
+    if (Ps.walk && !p->d_xT && p->mem.alloc(&p->d_xT, MB * P.nx) != hipSuccess)
+        return fail(GRAPE_ERR_ALLOC, "device allocation failed (sector walks)");
+    if (Ps.walk && (p->mem.alloc(&sb.Tc, R * Ps.nchunks * TS) != hipSuccess ||
+                    p->mem.alloc(&sb.wscr, 2 * (size_t)sc.nsec * lanes_pad * TS) != hipSuccess))
+        return fail(GRAPE_ERR_ALLOC, "device allocation failed (sector walks)");
+    if (p->mem.alloc(&sb.E, RE * P.Nt * P.nv * TS) != hipSuccess || p->mem.alloc(&sb.Q, RE * P.Nt * TS) != hipSuccess ||
+        p->mem.alloc(&sb.Mc, R * Ps.nchunks * TS) != hipSuccess || p->mem.alloc(&sb.Carry, R * Ps.nchunks * TS) != hipSuccess ||
+        p->mem.alloc(&sb.Ub, R * TS) != hipSuccess || p->mem.alloc(&sb.Msec, R * TS) != hipSuccess ||
+        p->mem.alloc(&sb.slots, R2 * P.Nt * nvg * TS) != hipSuccess || p->mem.alloc(&sb.ovf, RE * P.Nt * P.nv) != hipSuccess ||
+        p->mem.alloc(&sb.ovf2, R2 * P.Nt * nvg) != hipSuccess || p->mem.alloc(&sb.part, R * P.Nt * nvg) != hipSuccess ||
+        p->mem.alloc(&sb.sidx, sc.sidx.size()) != hipSuccess || p->mem.alloc(&sb.ops, sops.size()) != hipSuccess ||
+        p->mem.alloc(&sb.opsT, sopsT.size()) != hipSuccess ||
+        // (the image walk's images are lane-minor over its padded launch width: grape_walk.hpp img_index)
+        p->mem.alloc(&sb.Zl, (Ps.walk ? (size_t)sc.nsec * Ps.L * lanes_pad : R * P.Nt) * (ne && !Ps.gauge_lab ? P.nz : 0) * TS) != hipSuccess ||
+        p->mem.alloc(&sb.Wc, (Ps.walk ? R * ne * Ps.nchunks : 0) * TS) != hipSuccess ||
+        p->mem.alloc(&sb.Me, R * ne * Ps.nchunks * 3 * TS) != hipSuccess || p->mem.alloc(&sb.TotS, R * ne * TS) != hipSuccess ||
+        p->mem.alloc(&sb.MsecE, R * ne * TS) != hipSuccess || p->mem.alloc(&sb.part_err, R * ne * P.Nt * nvg) != hipSuccess)
+        return fail(GRAPE_ERR_ALLOC, "device allocation failed (sectors)");
+    if (hipMemcpy(sb.ops, sops.data(), sops.size() * sizeof(cd), hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(sb.opsT, sopsT.data(), sopsT.size() * sizeof(cd), hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(sb.sidx, sc.sidx.data(), sc.sidx.size() * sizeof(int), hipMemcpyHostToDevice) != hipSuccess)
+        return fail(GRAPE_ERR_HIP, "upload failed (sectors)");
+    Ps.ops = sb.ops;
+    Ps.opsT = sb.opsT;
+    return GRAPE_OK;
+}
+
+// E~ of every sector of a phase-covariant class, once per plan, into sb[cl].gEt: the merged walks' table
+// (grape_walk.hpp GRAPE_WALK_ET_SMEM: the walks' own exponential, so the same bits as a per-workgroup
+// copy) or, err: the lab-frame error walks' base table (1 + 2 ne matrices per sector).
+static int fill_gauge_table(grape_plan *p, int cl, bool err) {
+    DevProblem &Pc = p->Ps[cl];
+    const size_t nbm = (size_t)Pc.nsec * (err ? 1 + 2 * Pc.ne : 1), TS = (size_t)Pc.D * Pc.D;
+    grape_setup::DevicePool tmp;  // the fill's scratch
+    cd *scr = nullptr, *&gEt = p->sb[cl].gEt;
+    if (p->mem.alloc(&gEt, nbm * TS) != hipSuccess || tmp.alloc(&scr, nbm * 2 * TS) != hipSuccess)
+        return fail(GRAPE_ERR_ALLOC, err ? "device allocation failed (gauge error base)" : "device allocation failed (gauge base)");
+    const hipError_t e = err ? grape_walk::fill_gauge_err_base(Pc, Pc.nsec, scr, gEt, p->stream)
+                             : grape_walk::fill_gauge_base(Pc, Pc.nsec, scr, gEt, p->stream);
+    const hipError_t es = hipStreamSynchronize(p->stream);
+    if (e != hipSuccess || es != hipSuccess)
+        return fail(GRAPE_ERR_HIP, err ? "gauge error base fill failed" : "gauge base fill failed");
+    Pc.gauge_Et = gEt;
+    return GRAPE_OK;
+}
+
+// The two walk classes of the Rydberg layout in the pair kernels' order: pa the 4- (or 3-) level
+// class, pb the 2-level one.
+static void walk_pair_order(const grape_plan *p, int *pa, int *pb) {
+    *pa = 0;
+    *pb = 1;
+    if (p->ncls == 2 && grape_walk::pair_ok(p->Ps[1], p->Ps[0])) std::swap(*pa, *pb);
+}
+
+// throughput passes of the Rydberg layout with phase-covariant classes: class B (2 levels)
+// takes class A's chunking (fewer, longer chunks: its buffers, sized for its own count,
+// suffice) so that one lane can walk both (merged walks; GRAPE_OPT_NO_MERGE launches the
+// same chunking per class)
+static int setup_merge(grape_plan *p) {
+    if (p->ncls != 2) return GRAPE_OK;
+    const DevProblem &P = p->P;
+    int pa, pb;
+    walk_pair_order(p, &pa, &pb);
+    DevProblem &A = p->Ps[pa], &Bq = p->Ps[pb];
+    if (!(grape_walk::pair_ok(A, Bq) && A.D == 3 && A.gauge && Bq.gauge && A.gauge_a == Bq.gauge_a &&
+          A.scan_waves == kScanTiny && Bq.scan_waves == kScanTiny && A.nchunks <= Bq.nchunks && P.np == 1 && P.na <= 1))
+        return GRAPE_OK;
+    Bq.L = A.L;
+    Bq.nchunks = A.nchunks;
+    p->merged = !(P.opts & GRAPE_OPT_NO_MERGE) && grape_walk::merged_ok(A, Bq);
+    p->merge_pa = pa;
+    for (int cl = 0; p->merged && cl < 2; ++cl)  // E~ of both classes for the merged walks' scalar loads
+        if (int rc = fill_gauge_table(p, cl, false)) return rc;
+    return GRAPE_OK;
+}
+
+// latency-bound calls of the Rydberg layout with phase-covariant classes: one workgroup per
+// evaluation (grape_eval1.hip), with E~ of each class computed here once
+static int setup_eval1(grape_plan *p) {
+    const grape_proj::SectorHead &H = p->SH;
+    if (p->ncls != 2 || (long)p->max_batch > kEval1MaxBatch || (p->P.opts & GRAPE_OPT_NO_EVAL1)) return GRAPE_OK;
+    int pa, pb;
+    walk_pair_order(p, &pa, &pb);
+    const DevProblem &A = p->Ps[pa], &Bq = p->Ps[pb];
+    if (!grape_walk::pair_ok(A, Bq) || !grape_eval1::eligible(A, Bq, H)) return GRAPE_OK;
+    if (p->mem.alloc(&p->d_e1_Et, (size_t)A.D * A.D + 8) != hipSuccess ||
+        p->mem.alloc(&p->d_e1_scr, (size_t)2 * 2 * 16) != hipSuccess)
+        return fail(GRAPE_ERR_ALLOC, "device allocation failed (eval1)");
+    const hipError_t e = grape_eval1::prepare(A, Bq, p->d_e1_Et, p->d_e1_Et + (size_t)A.D * A.D, p->d_e1_scr, p->stream);
+    if (e != hipSuccess || hipStreamSynchronize(p->stream) != hipSuccess)
+        return fail(GRAPE_ERR_HIP, "eval1 preparation failed");
+    p->e1 = true;
+    p->e1_pa = pa;
+    const size_t tb = grape_eval1::tab_bytes(A, Bq, H);
+    if (p->mem.alloc(&p->d_e1_tab, std::max<size_t>(tb, 16)) != hipSuccess)
+        return fail(GRAPE_ERR_ALLOC, "device allocation failed (eval1)");
+    if (grape_eval1::tab_build(eval1_args(p, nullptr, nullptr, nullptr), p->d_e1_tab, p->stream) != hipSuccess ||
+        hipStreamSynchronize(p->stream) != hipSuccess)
+        return fail(GRAPE_ERR_HIP, "eval1 table build failed");
+    const char *tr = std::getenv("GRAPE_EVAL1_TRACE");
+    if (tr && tr[0] == '1' &&
+        (hipHostMalloc(reinterpret_cast<void **>(&p->e1_trace), 32 * sizeof(long long), hipHostMallocDefault) != hipSuccess ||
+         hipHostGetDevicePointer(reinterpret_cast<void **>(&p->e1_trace_d), p->e1_trace, 0) != hipSuccess))
+        return fail(GRAPE_ERR_ALLOC, "eval1 trace buffer");
+    return GRAPE_OK;
+}
+
+// The sector problems of every class and the head over the assembled U; then the merged walks, the
+// one-workgroup kernel and the auxiliary stream of two-class plans.
+static int setup_sectors(PlanBuild &b) {
+    if (b.ss.cls.empty()) return GRAPE_OK;
+    grape_plan *p = b.p;
+    if (int rc = setup_sector_head(b)) return rc;
+    grape_proj::SectorHead &H = p->SH;
+    for (int cl = 0; cl < (int)b.ss.cls.size(); ++cl) {
+        const SectorClass &sc = b.ss.cls[cl];
+        if (dispatch_lds_limits(sc.S) != hipSuccess) return fail(GRAPE_ERR_HIP, "cannot raise LDS limit");
+        std::vector<cd> sops((size_t)sc.nsec * b.n_ops * sc.S * sc.S), sopsT(sops.size());  // (rotated) operator blocks
+        grape_setup::to_tiles(b.sdesc.ops, b.n_ops, p->P.D, sc.sidx.data(), sc.nsec, sc.S, sops.data(), sopsT.data());
+        std::vector<int> gauge_n;
+        decide_class(b, sc, sops, p->Ps[cl], gauge_n);
+        if (int rc = alloc_class(b, cl, gauge_n, sops, sopsT)) return rc;
+        // the lab-frame error walks' base table, once per plan
+        if (p->Ps[cl].gauge_lab)
+            if (int rc = fill_gauge_table(p, cl, true)) return rc;
+        const grape_plan::SecBuf &sb = p->sb[cl];
+        H.S[cl] = sc.S;
+        H.nsec[cl] = sc.nsec;
+        H.sidx[cl] = sb.sidx;
+        H.Ub[cl] = sb.Ub;
+        H.Msec[cl] = sb.Msec;
+        H.TotS[cl] = sb.TotS;
+        H.MsecE[cl] = sb.MsecE;
+    }
+    p->ncls = (int)b.ss.cls.size();
+    if (int rc = setup_merge(p)) return rc;
+    if (int rc = setup_eval1(p)) return rc;
+    if (p->ncls == 2 && (hipStreamCreateWithFlags(&p->aux_stream, hipStreamNonBlocking) != hipSuccess ||
+                         hipEventCreateWithFlags(&p->ev_fork, hipEventDisableTiming) != hipSuccess ||
+                         hipEventCreateWithFlags(&p->ev_join, hipEventDisableTiming) != hipSuccess))
+        return fail(GRAPE_ERR_HIP, "cannot create the auxiliary stream");
+    return GRAPE_OK;
+}
+
+// 12 < d <= 64 with GRAPE_OPT_GENERAL_H0, operator basis: the operator images and the problem
+// ud_propagators_dev's dense branch exponentiates from (k_dexp_piv over the variant list): the terms,
+// scalars and x layout are the general path's
+static int setup_pivot_dense(PlanBuild &b) {
+    if (!b.rt.pivot || b.rt.tables) return GRAPE_OK;
+    grape_plan *p = b.p;
+    const int D = p->P.D;
+    if (grape_dense::set_lds_limits() != hipSuccess) return fail(GRAPE_ERR_HIP, "cannot raise LDS limit (dense)");
+    const size_t IMG = grape_dense::kImgDoubles;
+    std::vector<double> img((size_t)b.n_ops * IMG);
+    for (int o = 0; o < b.n_ops; ++o) to_dense_image(b.desc->ops + 2 * (size_t)o * D * D, D, img.data() + o * IMG);
+    if (p->mem.alloc(&p->dn_opimg, img.size()) != hipSuccess ||
+        hipMemcpy(p->dn_opimg, img.data(), img.size() * sizeof(double), hipMemcpyHostToDevice) != hipSuccess)
+        return fail(GRAPE_ERR_ALLOC, "device allocation failed (dense operator images)");
+    p->DP = grape_dense::DenseProblem{};
+    p->DP.P = p->P;
+    p->DP.opimg = p->dn_opimg;
+    p->dense = true;
+    return GRAPE_OK;
+}
+
+static int create_small(PlanBuild &b) {
+    if (int rc = setup_problem(b)) return rc;
+    if (int rc = alloc_whole_matrix(b)) return rc;
+    if (int rc = setup_general_h0(b)) return rc;
+    if (int rc = setup_sectors(b)) return rc;
+    return setup_pivot_dense(b);
 }
 
 // A fatal signal raised by code inside the library names its native frames on stderr before the
@@ -1212,570 +1706,27 @@ int grape_device_count(void) {
 int grape_plan_create(const grape_desc *desc, int device, grape_plan **out) {
     if (!desc || !out) return fail(GRAPE_ERR_INVALID, "null argument");
     *out = nullptr;
-    const int D = desc->ndim;
-    const bool tables = (desc->reserved[0] & GRAPE_DESC_HOST_TABLES) != 0;
-    if (D < 2 || desc->ntimes < 1 || desc->nparam < 1 || desc->nadd < 0 || desc->nerr < 0 ||
-        (!tables && desc->n_ops < 1))
-        return fail(GRAPE_ERR_INVALID, "bad dimensions in descriptor");
-    if (D > GRAPE_MAX_DENSE_DIM) return fail(GRAPE_ERR_UNSUPPORTED, "ndim > GRAPE_MAX_DENSE_DIM");
-    if (tables) {  // above GRAPE_MAX_SMALL_DIM: the general path with the dense exponential of the tables
-        if (!desc->projector_diag && !desc->projector) return fail(GRAPE_ERR_INVALID, "missing projector");
-    } else {
-        if (desc->nerr > 0 && !desc->err_term_offsets) return fail(GRAPE_ERR_INVALID, "missing err_term_offsets");
-        if (!desc->ops || !desc->h0_terms || desc->n_h0_terms < 1 || (!desc->projector_diag && !desc->projector) ||
-            !desc->target_terms ||
-            desc->n_target_terms < 1)
-            return fail(GRAPE_ERR_INVALID, "missing operator basis / terms / projector");
-    }
-    if (!(desc->t0 > 0) || !(desc->eps > 0)) return fail(GRAPE_ERR_INVALID, "t0 and eps must be positive");
-    int rc;
-    if (!tables && (rc = validate_terms(desc->h0_terms, desc->n_h0_terms, desc->n_ops, desc->nparam, desc->nadd, false, "H0")))
-        return rc;
-    if (!tables && (rc = validate_terms(desc->target_terms, desc->n_target_terms, desc->n_ops, desc->nparam, desc->nadd, true,
-                             "target")))
-        return rc;
     int n_err_terms = 0;
-    if (desc->nerr > 0 && !tables) {
-        for (int e = 0; e < desc->nerr; ++e)
-            if (desc->err_term_offsets[e + 1] <= desc->err_term_offsets[e])
-                return fail(GRAPE_ERR_INVALID, "each error source needs at least one term");
-        if (desc->err_term_offsets[0] != 0) return fail(GRAPE_ERR_INVALID, "err_term_offsets[0] must be 0");
-        n_err_terms = desc->err_term_offsets[desc->nerr];
-        if ((rc = validate_terms(desc->err_terms, n_err_terms, desc->n_ops, desc->nparam, desc->nadd, false,
-                                 "error source")))
-            return rc;
-    }
-    bool general_h0 = (desc->reserved[1] & GRAPE_OPT_GENERAL_H0) != 0;
-    if (!tables && !general_h0 && (rc = check_hermitian_terms(desc, desc->h0_terms, desc->n_h0_terms, "H0"))) {
-        if (rc != GRAPE_ERR_UNSUPPORTED || D > GRAPE_MAX_SMALL_DIM) return rc;
-        general_h0 = true;  // non-Hermitian H0: the general path serves it
-    }
-    // 12 < d <= 64 with the option: the general path over the dense engine's pivoted exponential
-    // (operator bases: below, after the general-path problem; host tables: launch_table_variants).
-    // Without the option nothing changes: a non-Hermitian H0 or error source is refused above.
-    const bool pivot = general_h0 && D > GRAPE_MAX_SMALL_DIM;
-    // closures above the small engine: host tables through the general path (materialised
-    // derivatives), each tabulated generator exponentiated by the dense engine (grape_dense.hip
-    // launch_table_variants; the host checks that the tables are Hermitian)
-    if (tables && D > GRAPE_MAX_SMALL_DIM) general_h0 = true;
-    // host tables: H0 / Herror are opaque closures that may read x_add, so every x_add call
-    // site of the reference is tabulated (UnitaryCalculations.jl:57-64, 87-95)
-    bool xadd_dep = tables && desc->nadd > 0;
-    for (int k = 0; k < (tables ? 0 : desc->n_h0_terms); ++k)
-        if (desc->h0_terms[k].var == 2) xadd_dep = true;
-    for (int k = 0; k < n_err_terms; ++k)
-        if (desc->err_terms[k].var == 2) xadd_dep = true;
-    // Hermitian error generators (the image walk's exponential is skew-Hermitian, grape_walk.hpp)
-    const bool err_herm = tables || hermitian_terms(desc, desc->err_terms, n_err_terms) == 0;
+    Route rt;
+    if (int rc = validate_desc(desc, &n_err_terms)) return rc;
+    if (int rc = choose_route(desc, n_err_terms, rt)) return rc;
     const ProjectorSetup ps = setup_projector(desc);
-    const double trP = ps.trP;
-    if (!(trP > 0)) return fail(GRAPE_ERR_INVALID, "projector trace must be positive");
+    if (!(ps.trP > 0)) return fail(GRAPE_ERR_INVALID, "projector trace must be positive");
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return fail(GRAPE_ERR_NO_DEVICE, "no HIP device");
     if (device < 0 || device >= ndev) return fail(GRAPE_ERR_NO_DEVICE, "device index out of range");
 
     grape_plan *p = new grape_plan();
-    for (int k = 0; k < (tables ? 0 : desc->n_h0_terms); ++k)
-        if (desc->h0_terms[k].var == GRAPE_VAR_TSTEP) p->uses_tstep = true;
-    p->device = device;
-    p->max_batch = desc->max_batch > 0 ? desc->max_batch : 256;
-    auto bail = [&](int code) {
+    int rc = open_plan(p, desc, device, rt);
+    if (!rc && desc->ndim > GRAPE_MAX_SMALL_DIM && !rt.tables && !rt.pivot) {
+        rc = create_dense(desc, p, rt.xadd_dep, ps, n_err_terms);
+    } else if (!rc) {
+        PlanBuild b{desc, p, rt, ps, n_err_terms};
+        rc = create_small(b);
+    }
+    if (rc) {  // (the message is set; the plan's pool returns whatever was allocated so far)
         free_plan(p);
-        return code;
-    };
-    if (hipSetDevice(device) != hipSuccess) return bail(fail(GRAPE_ERR_HIP, "hipSetDevice failed"));
-    if (hipStreamCreateWithFlags(&p->own_stream, hipStreamNonBlocking) != hipSuccess)
-        return bail(fail(GRAPE_ERR_HIP, "hipStreamCreate failed"));
-    p->stream = p->own_stream;
-    if (hipHostMalloc(reinterpret_cast<void **>(&p->h_status), sizeof(int), hipHostMallocDefault) != hipSuccess)
-        return bail(fail(GRAPE_ERR_ALLOC, "pinned allocation failed"));
-    *p->h_status = 0;
-    p->pivot = pivot;
-    if (D > GRAPE_MAX_SMALL_DIM && !tables && !pivot) {
-        const int rcd = create_dense(desc, p, xadd_dep, ps, n_err_terms);
-        if (rcd) return bail(rcd);
-        *out = p;
-        return GRAPE_OK;
-    }
-    if (D <= GRAPE_MAX_SMALL_DIM && dispatch_lds_limits(D) != hipSuccess)
-        return bail(fail(GRAPE_ERR_HIP, "cannot raise LDS limit"));
-
-    DevProblem &P = p->P;
-    p->tables = tables;
-    P.D = D;
-    P.Nt = desc->ntimes;
-    P.np = desc->nparam;
-    P.na = desc->nadd;
-    P.ne = desc->nerr;
-    P.nx = desc->nparam * desc->ntimes + desc->nadd;
-    P.n_h0 = desc->n_h0_terms;
-    P.n_tgt = desc->n_target_terms;
-    P.xadd_dep = xadd_dep ? 1 : 0;
-    // Propagator variants of one step (the closure call sites of UnitaryCalculations.jl:45-90):
-    //   0 nominal | dx: x_p + eps | dxa: x_add_q + eps (only if H0 reads x_add, otherwise
-    //   exp(A(x_add + eps)) == exp(A) bit for bit and the reference's difference is 0)
-    //   | ne > 0: dx2: x_p + eps2, then x_add_q + eps2 (xadd_dep) | per error e: err(eps),
-    //   err2(eps2), mix_p (x_p + eps2, err eps2), then mix_q (x_add_q + eps2, err eps2) (xadd_dep)
-    // The eps2 variants only feed the mixed stencils: skipped when ne == 0 (dead work).
-    // "u" indexes the nvg = np + nad gradient parameters: controls, then (xadd_dep) x_add;
-    // dx + u, dx2 + u and err_base + 2 + u are then the variants of parameter u.
-    const int nad = xadd_dep ? desc->nadd : 0;
-    std::vector<grape::VSpec> vs;
-    auto addv = [&](int var, int idx, double delta, int err, double errval) {
-        grape::VSpec v;
-        v.pert.var = var;
-        v.pert.index = idx;
-        v.pert.delta = delta;
-        v.err = err;
-        v.errval = errval;
-        vs.push_back(v);
-    };
-    addv(-1, 0, 0.0, -1, 0.0);
-    P.off_dx = (int)vs.size();
-    for (int q = 0; q < desc->nparam; ++q) addv(1, q, desc->eps, -1, 0.0);
-    P.off_dxa = (int)vs.size();
-    for (int q = 0; q < nad; ++q) addv(2, q, desc->eps, -1, 0.0);
-    P.off_dx2 = (int)vs.size();
-    if (desc->nerr > 0) {
-        for (int q = 0; q < desc->nparam; ++q) addv(1, q, desc->eps2, -1, 0.0);
-        for (int q = 0; q < nad; ++q) addv(2, q, desc->eps2, -1, 0.0);
-    }
-    P.off_err = (int)vs.size();
-    P.err_stride = 2 + desc->nparam + nad;
-    for (int e = 0; e < desc->nerr; ++e) {
-        addv(-1, 0, 0.0, e, desc->eps);
-        addv(-1, 0, 0.0, e, desc->eps2);
-        for (int q = 0; q < desc->nparam; ++q) addv(1, q, desc->eps2, e, desc->eps2);
-        for (int q = 0; q < nad; ++q) addv(2, q, desc->eps2, e, desc->eps2);
-    }
-    // E stores every variant for the error-source pipeline; without error sources
-    // only the nominal propagators are stored (k_expm_grad consumes the rest in place)
-    // host tables: every variant's propagator is stored (k_grad reads them back)
-    P.nv = (desc->nerr > 0 || tables) ? (int)vs.size() : 1;
-    P.nvg = desc->nparam + nad;
-    P.nz = P.nvg * (1 + desc->nerr) + desc->nerr;
-    P.dt = desc->t0 / desc->ntimes;
-    P.eps = desc->eps;
-    P.eps2 = desc->eps2;
-    P.inv_eps = 1.0 / desc->eps;
-    P.inv_eps2sq = 1.0 / (desc->eps2 * desc->eps2);
-    P.DD = trP * (trP + 1.0);
-    P.Dtr = trP;
-    // scan width: narrow once a launch can hold two evaluations per CU
-    int ncu = 256;
-    {
-        hipDeviceProp_t prop;
-        if (hipGetDeviceProperties(&prop, device) == hipSuccess && prop.multiProcessorCount > 0)
-            ncu = prop.multiProcessorCount;
-    }
-    P.opts = desc->reserved[1];
-    const int scan_override = desc->reserved[2];  // plan option: 1, 4, 8 or 16 waves (0: by batch size)
-    P.scan_waves = p->max_batch >= 2 * ncu ? kScanNarrow : kScanWide;
-    if (scan_override == kScanNarrow || scan_override == kScanWide) P.scan_waves = scan_override;
-    const int NG = P.scan_waves * (64 / D);
-    const int nc0 = std::min(NG, P.Nt);
-    P.L = (P.Nt + nc0 - 1) / nc0;
-    P.nchunks = (P.Nt + P.L - 1) / P.L;
-    P.sectors = 0;
-    P.nsec = 1;
-    P.sec_ops = 0;
-    p->general_h0 = general_h0;
-    // symmetry-adapted sectors: the sector path (operators, head) in the rotated basis when that
-    // splits the sectors further; the whole-matrix problem P keeps the caller's basis
-    const SymSetup sym = (general_h0 || tables) ? SymSetup{} : symmetry_setup(desc);
-    const grape_desc sdesc = sym.on ? sym.view(desc) : *desc;
-    const ProjectorSetup &sps = sym.on ? sym.ps : ps;
-    const SectorSetup ss = general_h0 ? SectorSetup{} : find_sectors(&sdesc, tables);
-    const bool sec = !ss.cls.empty();
-    p->symmetry = sym.on;
-    // whole-matrix workspace rows (none when sectors or the general-H0 path run)
-    const size_t FR = (sec || general_h0) ? 0 : (size_t)p->max_batch;
-
-    // operator basis: column-major interleaved -> row-major cd tiles (row builds)
-    // and column-major ones (the exp kernels build columns)
-    const int n_ops = tables ? 0 : desc->n_ops;
-    std::vector<cd> ops((size_t)n_ops * D * D), opsT(ops.size());
-    for (int o = 0; o < n_ops; ++o)
-        for (int r = 0; r < D; ++r)
-            for (int c = 0; c < D; ++c) {
-                const double *src = desc->ops + 2 * ((size_t)o * D * D + r + (size_t)c * D);
-                ops[(size_t)o * D * D + r * D + c] = cd{src[0], src[1]};
-                opsT[(size_t)o * D * D + c * D + r] = cd{src[0], src[1]};
-            }
-    const size_t MB = p->max_batch, T = (size_t)D * D;
-    bool ok = dalloc(&p->d_ops, ops.size()) == hipSuccess && dalloc(&p->d_opsT, opsT.size()) == hipSuccess &&
-              dalloc(&p->d_h0, std::max(desc->n_h0_terms, 0)) == hipSuccess &&
-              dalloc(&p->d_tgt, std::max(desc->n_target_terms, 0)) == hipSuccess &&
-              dalloc(&p->d_W, (size_t)D) == hipSuccess &&
-              dalloc(&p->d_E, FR * P.Nt * P.nv * T) == hipSuccess && dalloc(&p->d_Q, FR * P.Nt * T) == hipSuccess &&
-              dalloc(&p->d_Mc, FR * P.nchunks * T) == hipSuccess && dalloc(&p->d_x, MB * P.nx) == hipSuccess &&
-              dalloc(&p->d_F, MB) == hipSuccess && dalloc(&p->d_Fdx, MB * P.nx) == hipSuccess &&
-              dalloc(&p->d_part, MB * P.Nt * std::max(P.na, 1)) == hipSuccess &&
-              dalloc(&p->d_tgt_part, MB * std::max(P.na, 1)) == hipSuccess &&
-              dalloc(&p->d_ovf, FR * P.Nt * P.nv) == hipSuccess && dalloc(&p->d_ctrl, kCtrlInts) == hipSuccess &&
-              dalloc(&p->d_sink, T) == hipSuccess &&
-              dalloc(&p->d_vs, vs.size()) == hipSuccess;
-    const int nvg = P.np + (P.xadd_dep ? P.na : 0);
-    if (ok && P.ne == 0)
-        ok = dalloc(&p->d_ovf2, FR * P.Nt * nvg) == hipSuccess &&
-             dalloc(&p->d_ovf2_slots, FR * P.Nt * nvg * T) == hipSuccess;
-    if (ok && (P.ne > 0 || ps.general))  // carries and U: the error path and the general-projector heads
-        ok = dalloc(&p->d_Carry, FR * P.nchunks * T) == hipSuccess && dalloc(&p->d_Ub, FR * T) == hipSuccess;
-    if (ok && P.ne > 0)
-        ok = dalloc(&p->d_Me, FR * P.ne * P.nchunks * 3 * T) == hipSuccess &&
-             dalloc(&p->d_Fd2, MB * P.ne) == hipSuccess && dalloc(&p->d_Fd2dx, MB * P.ne * P.nx) == hipSuccess &&
-             dalloc(&p->d_err, (size_t)n_err_terms) == hipSuccess && dalloc(&p->d_err_off, (size_t)P.ne + 1) == hipSuccess;
-    if (ok && P.ne > 0) ok = dalloc(&p->d_Zl, FR * P.Nt * P.nz * T) == hipSuccess;
-    if (ok && P.ne > 0 && P.xadd_dep)
-        ok = dalloc(&p->d_part_err, MB * P.ne * P.Nt * P.na) == hipSuccess;
-    if (ok && tables)
-        ok = dalloc(&p->d_Htab, MB * P.Nt * P.nv * T) == hipSuccess &&
-             dalloc(&p->d_U0tab, MB * (1 + P.na) * T) == hipSuccess;
-    if (!ok) return bail(fail(GRAPE_ERR_ALLOC, "device allocation failed"));
-    if (hipMemset(p->d_ctrl, 0, kCtrlInts * sizeof(int)) != hipSuccess)
-        return bail(fail(GRAPE_ERR_HIP, "memset failed"));
-    if (hipMemcpy(p->d_vs, vs.data(), vs.size() * sizeof(grape::VSpec), hipMemcpyHostToDevice) != hipSuccess)
-        return bail(fail(GRAPE_ERR_HIP, "upload failed"));
-    if (P.ne > 0 && !tables &&
-        (hipMemcpy(p->d_err, desc->err_terms, n_err_terms * sizeof(Term), hipMemcpyHostToDevice) != hipSuccess ||
-         hipMemcpy(p->d_err_off, desc->err_term_offsets, (P.ne + 1) * sizeof(int), hipMemcpyHostToDevice) !=
-             hipSuccess))
-        return bail(fail(GRAPE_ERR_HIP, "upload failed"));
-    if ((!tables &&
-         (hipMemcpy(p->d_ops, ops.data(), ops.size() * sizeof(cd), hipMemcpyHostToDevice) != hipSuccess ||
-          hipMemcpy(p->d_opsT, opsT.data(), opsT.size() * sizeof(cd), hipMemcpyHostToDevice) != hipSuccess ||
-          hipMemcpy(p->d_h0, desc->h0_terms, desc->n_h0_terms * sizeof(Term), hipMemcpyHostToDevice) != hipSuccess ||
-          hipMemcpy(p->d_tgt, desc->target_terms, desc->n_target_terms * sizeof(Term), hipMemcpyHostToDevice) !=
-              hipSuccess)) ||
-        hipMemcpy(p->d_W, ps.W.data(), D * sizeof(double), hipMemcpyHostToDevice) != hipSuccess)
-        return bail(fail(GRAPE_ERR_HIP, "upload failed"));
-    if (int rcp = upload_projector(p, ps, P, MB * std::max(P.ne, 1))) return bail(rcp);
-    P.ops = p->d_ops;
-    P.opsT = p->d_opsT;
-    P.h0 = p->d_h0;
-    P.tgt = p->d_tgt;
-    P.err = p->d_err;
-    P.err_off = p->d_err_off;
-    P.vs = p->d_vs;
-    P.W = p->d_W;
-    if (general_h0) {  // the fidelity heads need P0 P and P as tiles (a diagonal projector: diag(w), diag(w != 0))
-        if (!ps.general) {
-            std::vector<cd> A(T, cd{0.0, 0.0}), Bm(T, cd{0.0, 0.0});
-            for (int i = 0; i < D; ++i) {
-                A[(size_t)i * D + i] = cd{ps.W[i], 0.0};
-                Bm[(size_t)i * D + i] = cd{ps.W[i] != 0.0 ? 1.0 : 0.0, 0.0};
-            }
-            if (dalloc(&p->d_PA, T) != hipSuccess || dalloc(&p->d_PB, T) != hipSuccess ||
-                hipMemcpy(p->d_PA, A.data(), T * sizeof(cd), hipMemcpyHostToDevice) != hipSuccess ||
-                hipMemcpy(p->d_PB, Bm.data(), T * sizeof(cd), hipMemcpyHostToDevice) != hipSuccess)
-                return bail(fail(GRAPE_ERR_ALLOC, "device allocation failed (general H0)"));
-            P.PA = p->d_PA;
-            P.PB = p->d_PB;
-        }
-        if (dalloc(&p->ud_Ci, (size_t)P.Nt * T) != hipSuccess || dalloc(&p->d_G, (1 + (size_t)P.ne) * T) != hipSuccess ||
-            (D > grape_unitary::kMaxD && dalloc(&p->d_fscr, (size_t)grape_unitary::kFidTiles * T) != hipSuccess))
-            return bail(fail(GRAPE_ERR_ALLOC, "device allocation failed (general H0)"));
-    }
-    if (sec) {  // the sector problems of every class and the head over the assembled U
-        std::vector<cd> A(T, cd{0.0, 0.0}), Bm(T, cd{0.0, 0.0});  // diagonal projector: A = diag(w), B = diag(w != 0)
-        for (int i = 0; i < D; ++i) {
-            A[(size_t)i * D + i] = cd{sps.W[i], 0.0};
-            Bm[(size_t)i * D + i] = cd{sps.W[i] != 0.0 ? 1.0 : 0.0, 0.0};
-        }
-        if (sym.on && sps.general) {
-            A = sps.A;
-            Bm = sps.B;
-        }
-        if (sym.on) {  // the head's own rotated projector tiles, weights and operators
-            std::vector<cd> rops((size_t)n_ops * T), ropsT(rops.size());
-            for (int o = 0; o < n_ops; ++o)
-                for (int r = 0; r < D; ++r)
-                    for (int c = 0; c < D; ++c) {
-                        const double *src = sym.ops.data() + 2 * ((size_t)o * T + r + (size_t)c * D);
-                        rops[(size_t)o * T + r * D + c] = cd{src[0], src[1]};
-                        ropsT[(size_t)o * T + c * D + r] = cd{src[0], src[1]};
-                    }
-            if (dalloc(&p->d_PA_sym, T) != hipSuccess || dalloc(&p->d_PB_sym, T) != hipSuccess ||
-                dalloc(&p->d_W_sym, (size_t)D) != hipSuccess || dalloc(&p->d_ops_sym, rops.size()) != hipSuccess ||
-                dalloc(&p->d_opsT_sym, ropsT.size()) != hipSuccess ||
-                hipMemcpy(p->d_PA_sym, A.data(), T * sizeof(cd), hipMemcpyHostToDevice) != hipSuccess ||
-                hipMemcpy(p->d_PB_sym, Bm.data(), T * sizeof(cd), hipMemcpyHostToDevice) != hipSuccess ||
-                hipMemcpy(p->d_W_sym, sps.W.data(), D * sizeof(double), hipMemcpyHostToDevice) != hipSuccess ||
-                hipMemcpy(p->d_ops_sym, rops.data(), rops.size() * sizeof(cd), hipMemcpyHostToDevice) != hipSuccess ||
-                hipMemcpy(p->d_opsT_sym, ropsT.data(), ropsT.size() * sizeof(cd), hipMemcpyHostToDevice) != hipSuccess)
-                return bail(fail(GRAPE_ERR_ALLOC, "device allocation failed (symmetry sectors)"));
-        } else if (!ps.general && (dalloc(&p->d_PA, T) != hipSuccess || dalloc(&p->d_PB, T) != hipSuccess ||
-                                   hipMemcpy(p->d_PA, A.data(), T * sizeof(cd), hipMemcpyHostToDevice) != hipSuccess ||
-                                   hipMemcpy(p->d_PB, Bm.data(), T * sizeof(cd), hipMemcpyHostToDevice) != hipSuccess))
-            return bail(fail(GRAPE_ERR_ALLOC, "device allocation failed (sectors)"));
-        if (dalloc(&p->d_fixed, ss.fixed.size()) != hipSuccess ||
-            (!ss.fixed.empty() && hipMemcpy(p->d_fixed, ss.fixed.data(), ss.fixed.size() * sizeof(int),
-                                            hipMemcpyHostToDevice) != hipSuccess))
-            return bail(fail(GRAPE_ERR_ALLOC, "device allocation failed (sectors)"));
-        grape_proj::SectorHead &H = p->SH;
-        H.P = P;
-        H.P.PA = sym.on ? p->d_PA_sym : p->d_PA;
-        H.P.PB = sym.on ? p->d_PB_sym : p->d_PB;
-        if (sym.on) {
-            H.P.W = p->d_W_sym;
-            H.P.ops = p->d_ops_sym;
-            H.P.opsT = p->d_opsT_sym;
-        }
-        H.ncls = (int)ss.cls.size();
-        H.fixed = p->d_fixed;
-        H.nfixed = (int)ss.fixed.size();
-        // diagonal projector and target, classes of <= 4 levels: the one-thread-per-evaluation head
-        // (grape_projector.hip k_sec_head_diag)
-        H.diag = !sps.general && !tables && !(P.opts & GRAPE_OPT_GENERAL_HEAD);
-        int rows = 0;  // the row-parallel head's lanes per evaluation (grape_projector.hip diag_group)
-        for (const SectorClass &sc : ss.cls) {
-            H.diag = H.diag && sc.S <= 4;
-            rows += sc.nsec * sc.S;
-        }
-        H.diag = H.diag && rows <= 32;
-        for (int k = 0; H.diag && k < desc->n_target_terms; ++k) {
-            const double *op = sdesc.ops + 2 * (size_t)desc->target_terms[k].op * D * D;
-            for (int i = 0; i < D; ++i)
-                for (int j = 0; j < D; ++j)
-                    if (i != j && (op[2 * (i + (size_t)j * D)] != 0.0 || op[2 * (i + (size_t)j * D) + 1] != 0.0))
-                        H.diag = 0;
-        }
-        for (int cl = 0; cl < (int)ss.cls.size(); ++cl) {
-            const SectorClass &sc = ss.cls[cl];
-            const int S = sc.S;
-            const size_t TS = (size_t)S * S, R = MB * sc.nsec;  // workspace rows: sub-evaluations
-            if (dispatch_lds_limits(S) != hipSuccess) return bail(fail(GRAPE_ERR_HIP, "cannot raise LDS limit"));
-            DevProblem &Ps = p->Ps[cl];
-            Ps = P;
-            Ps.D = S;
-            Ps.sectors = 1;
-            Ps.nsec = sc.nsec;
-            Ps.sec_ops = (size_t)n_ops * TS;
-            Ps.gen_proj = 0;
-            Ps.scan_waves = (long)R >= 8L * ncu ? kScanTiny : (long)R >= 2L * ncu ? kScanNarrow : kScanWide;
-            if (scan_override == kScanTiny || scan_override == kScanNarrow || scan_override == kScanWide)
-                Ps.scan_waves = scan_override;
-            // chunk walks (grape_walk.hpp): classes of <= kWalkMaxD levels; with error sources the
-            // image walk (k_walk_img), for any number of gradient parameters per step
-            // (its exponential keeps A skew-Hermitian in compressed form: Hermitian error generators only;
-            // a decay-rate error, -i e/2 |r><r|, keeps the stored-variant kernels)
-            Ps.walk = (S <= grape::kWalkMaxD && (P.ne == 0 || err_herm) && P.np <= grape::kWalkMaxNpA &&
-                       P.na <= grape::kWalkMaxNpA && !(P.opts & GRAPE_OPT_NO_WALK)) ? 1 : 0;
-            // the forward walk hands its propagators to the gradient walk (HBM, lane-minor) where the
-            // exponential is the expensive part: the 4-level class (grape_walk.hpp; measured C2 6.04 ->
-            // 6.52 M evals/s; for the 2-level class it lost, 0.72 -> 1.01 ms per pass)
-            // phase-covariant classes (grape_walk.hpp GAUGE): one exponential per walk lane
-            std::vector<int> gauge_n;
-            double gauge_a = 1.0;
-            // (with error sources: the phase-covariant image walk, one gradient parameter per step)
-            Ps.gauge = (Ps.walk && (P.ne == 0 || (P.nvg == 1 && P.ne <= grape::kGaugeMaxE)) &&
-                        !(P.opts & GRAPE_OPT_NO_GAUGE) && find_gauge(desc, sdesc, sc, gauge_a, gauge_n)) ? 1 : 0;
-            Ps.gauge_a = gauge_a;
-            Ps.gauge_n = nullptr;
-            Ps.gauge_ladder = 0;
-            if (Ps.gauge) {
-                Ps.gauge_ladder = 1;
-                for (size_t i = 0; i < gauge_n.size(); ++i)
-                    if (gauge_n[i] != (int)(i % (size_t)S)) Ps.gauge_ladder = 0;
-                int *gn = nullptr;
-                if (dalloc(&gn, gauge_n.size()) != hipSuccess) return bail(fail(GRAPE_ERR_ALLOC, "device allocation failed (gauge)"));
-                p->sb[cl].gauge_n = gn;
-                if (hipMemcpy(gn, gauge_n.data(), gauge_n.size() * sizeof(int), hipMemcpyHostToDevice) != hipSuccess)
-                    return bail(fail(GRAPE_ERR_HIP, "upload failed (gauge)"));
-                Ps.gauge_n = gn;
-            }
-            // error sources on a phase-covariant class: the lab-frame walks (no images, grape_walk.hpp
-            // GRAPE_WALK_ERR_LAB) when the base table's lanes fit one workgroup
-            Ps.gauge_lab = (GRAPE_WALK_ERR_LAB && Ps.gauge && P.ne > 0 &&
-                            sc.nsec * (1 + 2 * P.ne) <= grape::kLabBaseMaxLanes) ? 1 : 0;
-            Ps.gauge_Et = nullptr;
-            Ps.walk_store_e = Ps.walk && !Ps.gauge && P.ne == 0 && S >= grape::kWalkStoreMinD &&
-                              !(P.opts & GRAPE_OPT_WALK_RECOMPUTE) ? 1 : 0;
-            // latency-bound walk classes (fewer sub-evaluations than CUs, or the option): 16-wave scans,
-            // half-length walks (grape_launch.hpp kScanLatency)
-            // (GRAPE_LAB_LATENCY_SCAN: the lab-frame error walks too)
-            if (Ps.walk && (P.ne == 0 || (Ps.gauge_lab && GRAPE_LAB_LATENCY_SCAN)) &&
-                (scan_override == kScanLatency || (scan_override == 0 && (long)R < (long)ncu)))
-                Ps.scan_waves = kScanLatency;
-            // phase-covariant throughput classes: a step costs a few products instead of an
-            // exponential, so longer chunks (fewer per-lane prologues and a shorter scan) can pay
-            const int cdiv = (Ps.gauge && Ps.scan_waves == kScanTiny) ? (S == 2 ? GRAPE_GAUGE_CHUNK_DIV2 : GRAPE_GAUGE_CHUNK_DIV) : 1;
-            int ncs = std::max(1, std::min(Ps.scan_waves * (64 / S) / cdiv, P.Nt));
-            if (Ps.gauge && Ps.scan_waves == kScanTiny && S == 3 && P.ne == 0)
-                ncs = merged_chunk_count((long)MB, P.Nt, ncs, ncu);
-            // the lab-frame error walks' throughput chunking (A/B knobs; 0: the formula above)
-            if (Ps.gauge_lab && Ps.scan_waves == kScanTiny) {
-                const int lc = S >= 4 ? GRAPE_LAB_CHUNKS4 : GRAPE_LAB_CHUNKS2;
-                if (lc > 0) ncs = std::max(1, std::min(lc, P.Nt));
-            }
-            Ps.L = (P.Nt + ncs - 1) / ncs;
-            Ps.nchunks = (P.Nt + Ps.L - 1) / Ps.L;
-            grape_plan::SecBuf &b = p->sb[cl];
-            const size_t ne = (size_t)P.ne, R2 = (P.ne > 0 || Ps.walk) ? 0 : R;  // k_expm_grad parking: no error sources only
-            const size_t RE = Ps.walk ? 0 : R;  // the walks store no E / Q
-            const size_t lanes_pad = (MB * Ps.nchunks + grape::kWalkBlockA - 1) / grape::kWalkBlockA * grape::kWalkBlockA;
-            // stored propagators: D*D elements + the diagonal shift per (step, sector) (grape_walk.hpp kEwStride)
-            if (Ps.walk_store_e && dalloc(&b.Ew, (size_t)sc.nsec * Ps.L * (TS + 1) * lanes_pad) != hipSuccess)
-                return bail(fail(GRAPE_ERR_ALLOC, "device allocation failed (sector walks)"));
-            if (Ps.walk && !p->d_xT && dalloc(&p->d_xT, MB * P.nx) != hipSuccess)
-                return bail(fail(GRAPE_ERR_ALLOC, "device allocation failed (sector walks)"));
-            if (Ps.walk && (dalloc(&b.Tc, R * Ps.nchunks * TS) != hipSuccess ||
-                            dalloc(&b.wscr, 2 * (size_t)sc.nsec * ((MB * Ps.nchunks + grape::kWalkBlockA - 1) /
-                                                                  grape::kWalkBlockA * grape::kWalkBlockA) * TS) != hipSuccess))
-                return bail(fail(GRAPE_ERR_ALLOC, "device allocation failed (sector walks)"));
-            if (dalloc(&b.E, RE * P.Nt * P.nv * TS) != hipSuccess || dalloc(&b.Q, RE * P.Nt * TS) != hipSuccess ||
-                dalloc(&b.Mc, R * Ps.nchunks * TS) != hipSuccess || dalloc(&b.Carry, R * Ps.nchunks * TS) != hipSuccess ||
-                dalloc(&b.Ub, R * TS) != hipSuccess || dalloc(&b.Msec, R * TS) != hipSuccess ||
-                dalloc(&b.slots, R2 * P.Nt * nvg * TS) != hipSuccess || dalloc(&b.ovf, RE * P.Nt * P.nv) != hipSuccess ||
-                dalloc(&b.ovf2, R2 * P.Nt * nvg) != hipSuccess || dalloc(&b.part, R * P.Nt * nvg) != hipSuccess ||
-                dalloc(&b.sidx, sc.sidx.size()) != hipSuccess || dalloc(&b.ops, (size_t)sc.nsec * n_ops * TS) != hipSuccess ||
-                dalloc(&b.opsT, (size_t)sc.nsec * n_ops * TS) != hipSuccess ||
-                // (the image walk's images are lane-minor over its padded launch width: grape_walk.hpp img_index)
-                dalloc(&b.Zl, (Ps.walk ? (size_t)sc.nsec * Ps.L * lanes_pad : R * P.Nt) * (ne && !Ps.gauge_lab ? P.nz : 0) * TS) != hipSuccess ||
-                dalloc(&b.Wc, (Ps.walk ? R * ne * Ps.nchunks : 0) * TS) != hipSuccess ||
-                dalloc(&b.Me, R * ne * Ps.nchunks * 3 * TS) != hipSuccess || dalloc(&b.TotS, R * ne * TS) != hipSuccess ||
-                dalloc(&b.MsecE, R * ne * TS) != hipSuccess || dalloc(&b.part_err, R * ne * P.Nt * nvg) != hipSuccess)
-                return bail(fail(GRAPE_ERR_ALLOC, "device allocation failed (sectors)"));
-            std::vector<cd> sops((size_t)sc.nsec * n_ops * TS), sopsT(sops.size());
-            for (int w = 0; w < sc.nsec; ++w)
-                for (int o = 0; o < n_ops; ++o)
-                    for (int a = 0; a < S; ++a)
-                        for (int c = 0; c < S; ++c) {
-                            const int gi = sc.sidx[(size_t)w * S + a], gj = sc.sidx[(size_t)w * S + c];
-                            cd v{0.0, 0.0};
-                            if (gi >= 0 && gj >= 0) {  // (rotated) column-major operator
-                                const double *sv = sdesc.ops + 2 * ((size_t)o * T + gi + (size_t)gj * D);
-                                v = cd{sv[0], sv[1]};
-                            }
-                            const size_t base = ((size_t)w * n_ops + o) * TS;
-                            sops[base + (size_t)a * S + c] = v;
-                            sopsT[base + (size_t)c * S + a] = v;
-                        }
-            if (hipMemcpy(b.ops, sops.data(), sops.size() * sizeof(cd), hipMemcpyHostToDevice) != hipSuccess ||
-                hipMemcpy(b.opsT, sopsT.data(), sopsT.size() * sizeof(cd), hipMemcpyHostToDevice) != hipSuccess ||
-                hipMemcpy(b.sidx, sc.sidx.data(), sc.sidx.size() * sizeof(int), hipMemcpyHostToDevice) != hipSuccess)
-                return bail(fail(GRAPE_ERR_HIP, "upload failed (sectors)"));
-            Ps.ops = b.ops;
-            Ps.opsT = b.opsT;
-            if (Ps.gauge_lab) {  // the lab-frame error walks' base table, once per plan
-                const size_t nbm = (size_t)sc.nsec * (1 + 2 * P.ne);
-                cd *scr = nullptr;
-                if (dalloc(&b.gEt, nbm * TS) != hipSuccess || dalloc(&scr, nbm * 2 * TS) != hipSuccess) {
-                    if (scr) (void)hipFree(scr);
-                    return bail(fail(GRAPE_ERR_ALLOC, "device allocation failed (gauge error base)"));
-                }
-                const hipError_t e = grape_walk::fill_gauge_err_base(Ps, sc.nsec, scr, b.gEt, p->stream);
-                const hipError_t es = hipStreamSynchronize(p->stream);
-                (void)hipFree(scr);
-                if (e != hipSuccess || es != hipSuccess) return bail(fail(GRAPE_ERR_HIP, "gauge error base fill failed"));
-                Ps.gauge_Et = b.gEt;
-            }
-            // twin sectors (grape_walk.hpp TWIN): two walk sectors whose blocks of every operator H0
-            // and the error sources use are identical, with the same padding -- one exponential
-            // per step serves both (the 2-level Rydberg sectors at equal Rabi frequencies)
-            Ps.twin = 0;
-            // (S == 2 only: launch<2> is the one launcher that runs a class with two sectors per lane)
-            if (Ps.walk && P.ne == 0 && sc.nsec == 2 && S == 2 && !Ps.walk_store_e && !(P.opts & GRAPE_OPT_NO_TWIN)) {
-                bool same = true;
-                for (int a = 0; a < S; ++a) same = same && ((sc.sidx[a] < 0) == (sc.sidx[S + a] < 0));
-                std::vector<char> used(n_ops, 0);
-                for (int t = 0; t < desc->n_h0_terms; ++t) used[desc->h0_terms[t].op] = 1;
-                for (int o = 0; same && o < n_ops; ++o)
-                    if (used[o])
-                        same = std::memcmp(&sops[(size_t)o * TS], &sops[((size_t)n_ops + o) * TS], TS * sizeof(cd)) == 0;
-                Ps.twin = same ? 1 : 0;
-            }
-            H.S[cl] = S;
-            H.nsec[cl] = sc.nsec;
-            H.sidx[cl] = b.sidx;
-            H.Ub[cl] = b.Ub;
-            H.Msec[cl] = b.Msec;
-            H.TotS[cl] = b.TotS;
-            H.MsecE[cl] = b.MsecE;
-        }
-        p->ncls = (int)ss.cls.size();
-        // throughput passes of the Rydberg layout with phase-covariant classes: class B (2 levels)
-        // takes class A's chunking (fewer, longer chunks: its buffers, sized for its own count,
-        // suffice) so that one lane can walk both (merged walks; GRAPE_OPT_NO_MERGE launches the
-        // same chunking per class)
-        if (p->ncls == 2) {
-            int pa = 0, pb = 1;
-            if (grape_walk::pair_ok(p->Ps[1], p->Ps[0])) std::swap(pa, pb);
-            DevProblem &A = p->Ps[pa], &Bq = p->Ps[pb];
-            if (grape_walk::pair_ok(A, Bq) && A.D == 3 && A.gauge && Bq.gauge && A.gauge_a == Bq.gauge_a &&
-                A.scan_waves == kScanTiny && Bq.scan_waves == kScanTiny && A.nchunks <= Bq.nchunks && P.np == 1 &&
-                P.na <= 1) {
-                Bq.L = A.L;
-                Bq.nchunks = A.nchunks;
-                p->merged = !(P.opts & GRAPE_OPT_NO_MERGE) && grape_walk::merged_ok(A, Bq);
-                p->merge_pa = pa;
-                // E~ of both classes, once per plan, for the merged walks' scalar loads (grape_walk.hpp
-                // GRAPE_WALK_ET_SMEM): the walks' own exponential, so the same bits as a per-workgroup copy
-                for (int cl = 0; p->merged && cl < 2; ++cl) {
-                    DevProblem &Pc = p->Ps[cl];
-                    const int nsec = ss.cls[cl].nsec, S = Pc.D;
-                    cd *scr = nullptr;
-                    if (dalloc(&p->sb[cl].gEt, (size_t)nsec * S * S) != hipSuccess ||
-                        dalloc(&scr, (size_t)nsec * 2 * S * S) != hipSuccess) {
-                        if (scr) (void)hipFree(scr);
-                        return bail(fail(GRAPE_ERR_ALLOC, "device allocation failed (gauge base)"));
-                    }
-                    const hipError_t e = grape_walk::fill_gauge_base(Pc, nsec, scr, p->sb[cl].gEt, p->stream);
-                    const hipError_t es = hipStreamSynchronize(p->stream);
-                    (void)hipFree(scr);
-                    if (e != hipSuccess || es != hipSuccess) return bail(fail(GRAPE_ERR_HIP, "gauge base fill failed"));
-                    Pc.gauge_Et = p->sb[cl].gEt;
-                }
-            }
-        }
-        // latency-bound calls of the Rydberg layout with phase-covariant classes: one workgroup per
-        // evaluation (grape_eval1.hip), with E~ of each class computed here once
-        if (p->ncls == 2 && (long)MB <= kEval1MaxBatch && !(P.opts & GRAPE_OPT_NO_EVAL1)) {
-            int pa = 0, pb = 1;
-            if (grape_walk::pair_ok(p->Ps[1], p->Ps[0])) std::swap(pa, pb);
-            if (grape_walk::pair_ok(p->Ps[pa], p->Ps[pb]) && grape_eval1::eligible(p->Ps[pa], p->Ps[pb], H)) {
-                if (dalloc(&p->d_e1_Et, (size_t)p->Ps[pa].D * p->Ps[pa].D + 8) != hipSuccess ||
-                    dalloc(&p->d_e1_scr, (size_t)2 * 2 * 16) != hipSuccess)
-                    return bail(fail(GRAPE_ERR_ALLOC, "device allocation failed (eval1)"));
-                const hipError_t e = grape_eval1::prepare(p->Ps[pa], p->Ps[pb], p->d_e1_Et,
-                                                          p->d_e1_Et + (size_t)p->Ps[pa].D * p->Ps[pa].D, p->d_e1_scr,
-                                                          p->stream);
-                if (e != hipSuccess || hipStreamSynchronize(p->stream) != hipSuccess)
-                    return bail(fail(GRAPE_ERR_HIP, "eval1 preparation failed"));
-                p->e1 = true;
-                p->e1_pa = pa;
-                const size_t tb = grape_eval1::tab_bytes(p->Ps[pa], p->Ps[pb], H);
-                if (hipMalloc(reinterpret_cast<void **>(&p->d_e1_tab), std::max<size_t>(tb, 16)) != hipSuccess)
-                    return bail(fail(GRAPE_ERR_ALLOC, "device allocation failed (eval1)"));
-                if (grape_eval1::tab_build(eval1_args(p, nullptr, nullptr, nullptr), p->d_e1_tab, p->stream) != hipSuccess ||
-                    hipStreamSynchronize(p->stream) != hipSuccess)
-                    return bail(fail(GRAPE_ERR_HIP, "eval1 table build failed"));
-                const char *tr = std::getenv("GRAPE_EVAL1_TRACE");
-                if (tr && tr[0] == '1' &&
-                    (hipHostMalloc(reinterpret_cast<void **>(&p->e1_trace), 32 * sizeof(long long), hipHostMallocDefault) != hipSuccess ||
-                     hipHostGetDevicePointer(reinterpret_cast<void **>(&p->e1_trace_d), p->e1_trace, 0) != hipSuccess))
-                    return bail(fail(GRAPE_ERR_ALLOC, "eval1 trace buffer"));
-            }
-        }
-        if (p->ncls == 2 && (hipStreamCreateWithFlags(&p->aux_stream, hipStreamNonBlocking) != hipSuccess ||
-                             hipEventCreateWithFlags(&p->ev_fork, hipEventDisableTiming) != hipSuccess ||
-                             hipEventCreateWithFlags(&p->ev_join, hipEventDisableTiming) != hipSuccess))
-            return bail(fail(GRAPE_ERR_HIP, "cannot create the auxiliary stream"));
-    }
-    if (pivot && !tables) {
-        // the operator images and the problem ud_propagators_dev's dense branch exponentiates from
-        // (k_dexp_piv over the variant list): the terms, scalars and x layout are the general path's
-        if (grape_dense::set_lds_limits() != hipSuccess) return bail(fail(GRAPE_ERR_HIP, "cannot raise LDS limit (dense)"));
-        const size_t IMG = grape_dense::kImgDoubles;
-        std::vector<double> img((size_t)n_ops * IMG);
-        for (int o = 0; o < n_ops; ++o) to_dense_image(desc->ops + 2 * (size_t)o * D * D, D, img.data() + o * IMG);
-        if (dalloc(&p->dn_opimg, img.size()) != hipSuccess ||
-            hipMemcpy(p->dn_opimg, img.data(), img.size() * sizeof(double), hipMemcpyHostToDevice) != hipSuccess)
-            return bail(fail(GRAPE_ERR_ALLOC, "device allocation failed (dense operator images)"));
-        p->DP = grape_dense::DenseProblem{};
-        p->DP.P = P;
-        p->DP.opimg = p->dn_opimg;
-        p->dense = true;
+        return rc;
     }
     *out = p;
     return GRAPE_OK;
@@ -1823,7 +1774,13 @@ int grape_plan_set_stream(grape_plan *plan, void *stream) {
     return GRAPE_OK;
 }
 
-static std::vector<grape::VSpec> ud_variants(const DevProblem &P0, grape_unitary::UProblem &UP);
+// every closure call site of UnitaryCalculations.jl:45-95 as a propagator variant, in the
+// layout of grape_unitary::UProblem (= the host-table layout of grape_fidelity_grad_tables
+// with every x_add site present), and the assembly's slots per step
+static grape_setup::Variants ud_variants(const DevProblem &P0) {
+    return grape_setup::build_variants(P0.np, P0.na, P0.ne, P0.eps, P0.eps2, true);
+}
+static int ud_nslots(const DevProblem &P0) { return P0.np + P0.na + P0.ne + P0.ne * (P0.np + P0.na); }
 static std::vector<grape::VSpec> ud_setup(grape_plan *p, grape_unitary::UProblem &UP, grape_unitary::UBuffers &UB);
 static int ud_alloc(grape_plan *p);
 static int ud_propagators_dev(grape_plan *p, const double *d_x, int nv, const cd *d_Htab);
@@ -1975,8 +1932,8 @@ static int enqueue(grape_plan *p, int nb, const double *d_x, double *d_F, double
         // Latency-bound calls of the Rydberg layout: both classes' walks (and scans) in ONE launch per
         // stage (grape_walk_api.hpp launch_pair) -- neither a graph branch nor a second stream overlaps
         // them inside a captured graph on this runtime.  pa: the 4- (or 3-) level class, pb: the 2-level one.
-        int pa = 0, pb = 1;
-        if (p->ncls == 2 && grape_walk::pair_ok(p->Ps[1], p->Ps[0])) std::swap(pa, pb);
+        int pa, pb;
+        walk_pair_order(p, &pa, &pb);
         // (small calls only: a pair kernel runs the 2-level class at the 4-level class's occupancy)
         const bool pair = p->ncls == 2 && nb <= kPairMaxBatch && !(p->P.opts & GRAPE_OPT_NO_PAIR) &&
                           p->Ps[0].scan_waves == kScanLatency &&
@@ -2291,7 +2248,7 @@ static int fidelity_grad_graph(grape_plan *p, int nb, const double *x, double *F
         const size_t cap = graph_out(p, 1).capacity;
         if (!pin(&p->h_x, B * nx) || !pin(&p->h_F, cap))
             return fail(GRAPE_ERR_ALLOC, "pinned allocation failed (graph path)");
-        if (dalloc(&p->d_gout, cap) != hipSuccess)
+        if (p->mem.alloc(&p->d_gout, cap) != hipSuccess)
             return fail(GRAPE_ERR_ALLOC, "device allocation failed (graph path)");
     }
     if (p->e1) {
@@ -2335,6 +2292,19 @@ static int fidelity_grad_graph(grape_plan *p, int nb, const double *x, double *F
     return GRAPE_OK;
 }
 
+// the results of workspace rows [0, nb) into the caller's host arrays at evaluation b0; synchronises
+static int results_to_host(grape_plan *p, int b0, int nb, double *F, double *F_dx, double *F_d2err, double *F_d2err_dx) {
+    const size_t nx = p->P.nx, ne = p->P.ne;
+    HIPCHECK(hipMemcpyAsync(F + b0, p->d_F, nb * sizeof(double), hipMemcpyDeviceToHost, p->stream));
+    if (ne > 0) {
+        HIPCHECK(hipMemcpyAsync(F_d2err + b0 * ne, p->d_Fd2, nb * ne * sizeof(double), hipMemcpyDeviceToHost, p->stream));
+        HIPCHECK(hipMemcpyAsync(F_d2err_dx + b0 * ne * nx, p->d_Fd2dx, nb * ne * nx * sizeof(double),
+                                hipMemcpyDeviceToHost, p->stream));
+    }
+    HIPCHECK(hipMemcpyAsync(F_dx + b0 * nx, p->d_Fdx, nb * nx * sizeof(double), hipMemcpyDeviceToHost, p->stream));
+    return grape_plan_synchronize(p);
+}
+
 int grape_fidelity_grad(grape_plan *p, int nbatch, const double *x, double *F, double *F_dx, double *F_d2err,
                         double *F_d2err_dx) {
     if (!p || nbatch < 0 || (nbatch > 0 && (!x || !F || !F_dx))) return fail(GRAPE_ERR_INVALID, "bad argument");
@@ -2348,20 +2318,8 @@ int grape_fidelity_grad(grape_plan *p, int nbatch, const double *x, double *F, d
         const int nb = std::min(p->max_batch, nbatch - b0);
         HIPCHECK(hipMemcpyAsync(p->d_x, x + (size_t)b0 * nx, (size_t)nb * nx * sizeof(double),
                                 hipMemcpyHostToDevice, p->stream));
-        int rc = enqueue_call(p, nb, p->d_x, p->d_F, p->d_Fdx, p->d_Fd2, p->d_Fd2dx);
-        if (rc) return rc;
-        HIPCHECK(hipMemcpyAsync(F + b0, p->d_F, nb * sizeof(double), hipMemcpyDeviceToHost, p->stream));
-        if (p->P.ne > 0) {
-            const int ne = p->P.ne;
-            HIPCHECK(hipMemcpyAsync(F_d2err + (size_t)b0 * ne, p->d_Fd2, (size_t)nb * ne * sizeof(double),
-                                    hipMemcpyDeviceToHost, p->stream));
-            HIPCHECK(hipMemcpyAsync(F_d2err_dx + (size_t)b0 * ne * nx, p->d_Fd2dx,
-                                    (size_t)nb * ne * nx * sizeof(double), hipMemcpyDeviceToHost, p->stream));
-        }
-        HIPCHECK(hipMemcpyAsync(F_dx + (size_t)b0 * nx, p->d_Fdx, (size_t)nb * nx * sizeof(double),
-                                hipMemcpyDeviceToHost, p->stream));
-        rc = grape_plan_synchronize(p);
-        if (rc) return rc;
+        if (int rc = enqueue_call(p, nb, p->d_x, p->d_F, p->d_Fdx, p->d_Fd2, p->d_Fd2dx)) return rc;
+        if (int rc = results_to_host(p, b0, nb, F, F_dx, F_d2err, F_d2err_dx)) return rc;
     }
     return GRAPE_OK;
 }
@@ -2373,9 +2331,9 @@ static int slice_check(grape_plan *p) {
         return fail(GRAPE_ERR_UNSUPPORTED, "time slices: dense-engine operator-basis plans without error sources, "
                                            "x_add, a general projector or step-index terms");
     const size_t T = (size_t)p->P.D * p->P.D;
-    if (!p->dn_Ub && dalloc(&p->dn_Ub, (size_t)p->max_batch * grape_dense::kImgDoubles) != hipSuccess)
+    if (!p->dn_Ub && p->mem.alloc(&p->dn_Ub, (size_t)p->max_batch * grape_dense::kImgDoubles) != hipSuccess)
         return fail(GRAPE_ERR_ALLOC, "device allocation failed (time slices)");
-    if (!p->d_slice && dalloc(&p->d_slice, 2 * T) != hipSuccess)
+    if (!p->d_slice && p->mem.alloc(&p->d_slice, 2 * T) != hipSuccess)
         return fail(GRAPE_ERR_ALLOC, "device allocation failed (time slices)");
     return GRAPE_OK;
 }
@@ -2449,20 +2407,8 @@ int grape_fidelity_grad_tables(grape_plan *p, int nbatch, const double *x, const
                                 p->stream));
         HIPCHECK(hipMemcpyAsync(p->d_U0tab, U0 + 2 * b0 * usz, nb * usz * sizeof(cd), hipMemcpyHostToDevice,
                                 p->stream));
-        int rc = enqueue(p, nb, p->d_x, p->d_F, p->d_Fdx, p->d_Fd2, p->d_Fd2dx);
-        if (rc) return rc;
-        HIPCHECK(hipMemcpyAsync(p->h_status, p->d_ctrl + 2, sizeof(int), hipMemcpyDeviceToHost, p->stream));
-        if (P.ne > 0) {
-            HIPCHECK(hipMemcpyAsync(F_d2err + b0 * P.ne, p->d_Fd2, nb * P.ne * sizeof(double), hipMemcpyDeviceToHost,
-                                    p->stream));
-            HIPCHECK(hipMemcpyAsync(F_d2err_dx + b0 * P.ne * nx, p->d_Fd2dx, nb * P.ne * nx * sizeof(double),
-                                    hipMemcpyDeviceToHost, p->stream));
-        }
-        HIPCHECK(hipMemcpyAsync(F + b0, p->d_F, nb * sizeof(double), hipMemcpyDeviceToHost, p->stream));
-        HIPCHECK(hipMemcpyAsync(F_dx + b0 * nx, p->d_Fdx, nb * nx * sizeof(double), hipMemcpyDeviceToHost,
-                                p->stream));
-        rc = grape_plan_synchronize(p);
-        if (rc) return rc;
+        if (int rc = enqueue_call(p, nb, p->d_x, p->d_F, p->d_Fdx, p->d_Fd2, p->d_Fd2dx)) return rc;
+        if (int rc = results_to_host(p, b0, nb, F, F_dx, F_d2err, F_d2err_dx)) return rc;
     }
     return GRAPE_OK;
 }
@@ -2492,29 +2438,18 @@ static int ud_alloc(grape_plan *p) {
     if (p->ud_vs) return GRAPE_OK;
     const DevProblem &P = p->P;
     const size_t T = (size_t)P.D * P.D, Nt = P.Nt, np = P.np, na = P.na, ne = P.ne;
-    const size_t nv = 1 + (np + na) * (ne > 0 ? 2 : 1) + ne * (2 + np + na);
-    const size_t nslots = np + na + ne + ne * (np + na);
+    const size_t nv = ud_variants(P).vs.size(), nslots = ud_nslots(P);
     const size_t nout = T * (np * Nt + na + ne + np * Nt * ne + na * ne + Nt * ne);
-    bool ok = dalloc(&p->ud_vs, nv) == hipSuccess && dalloc(&p->ud_E, Nt * nv * T) == hipSuccess &&
-                    dalloc(&p->ud_ovf, Nt * nv) == hipSuccess && dalloc(&p->ud_C, Nt * T) == hipSuccess &&
-                    dalloc(&p->ud_V, Nt * nslots * T) == hipSuccess &&
-                    dalloc(&p->ud_S, Nt * std::max<size_t>(ne, 1) * T) == hipSuccess && dalloc(&p->ud_out, nout) == hipSuccess;
-    if (ok && P.D > grape_unitary::kMaxD) ok = dalloc(&p->ud_gscr, grape_unitary::scratch_elems(P.D)) == hipSuccess;
+    bool ok = p->mem.alloc(&p->ud_vs, nv) == hipSuccess && p->mem.alloc(&p->ud_E, Nt * nv * T) == hipSuccess &&
+                    p->mem.alloc(&p->ud_ovf, Nt * nv) == hipSuccess && p->mem.alloc(&p->ud_C, Nt * T) == hipSuccess &&
+                    p->mem.alloc(&p->ud_V, Nt * nslots * T) == hipSuccess &&
+                    p->mem.alloc(&p->ud_S, Nt * std::max<size_t>(ne, 1) * T) == hipSuccess && p->mem.alloc(&p->ud_out, nout) == hipSuccess;
+    if (ok && P.D > grape_unitary::kMaxD) ok = p->mem.alloc(&p->ud_gscr, grape_unitary::scratch_elems(P.D)) == hipSuccess;
     if (ok && (p->dense || P.D > GRAPE_MAX_SMALL_DIM))
-        ok = dalloc(&p->ud_Eimg, Nt * nv * grape_dense::kImgDoubles) == hipSuccess;
+        ok = p->mem.alloc(&p->ud_Eimg, Nt * nv * grape_dense::kImgDoubles) == hipSuccess;
     if (ok && p->tables && P.D > GRAPE_MAX_SMALL_DIM)
-        ok = dalloc(&p->ud_Aimg, Nt * nv * grape_dense::kImgDoubles) == hipSuccess;
+        ok = p->mem.alloc(&p->ud_Aimg, Nt * nv * grape_dense::kImgDoubles) == hipSuccess;
     return ok ? GRAPE_OK : fail(GRAPE_ERR_ALLOC, "device allocation failed (single-evaluation workspace)");
-}
-
-static hipError_t dispatch_expm_table(int D, const DevProblem &P, const DevBatch &B, hipStream_t st) {
-    switch (D) {
-#define CASE(d) \
-    case d: return grape_host::launch_expm_table<d>(P, B, st);
-        GRAPE_DIMS(CASE)
-#undef CASE
-    }
-    return hipErrorInvalidValue;
 }
 
 // Propagator table E[k][v] of ONE x into the ud workspace, for the variant list already in
@@ -2674,39 +2609,6 @@ int grape_expectation_values_tables(grape_plan *p, const double *x, const double
     return expectation_to(p, x, H0, Oerr, ev);
 }
 
-// every closure call site of UnitaryCalculations.jl:45-95 as a propagator variant, in the
-// layout of grape_unitary::UProblem (= the host-table layout of grape_fidelity_grad_tables
-// with every x_add site present)
-static std::vector<grape::VSpec> ud_variants(const DevProblem &P0, grape_unitary::UProblem &UP) {
-    const int np = P0.np, na = P0.na, ne = P0.ne;
-    std::vector<grape::VSpec> vs;
-    auto addv = [&](int var, int idx, double delta, int err, double errval) {
-        grape::VSpec v;
-        v.pert.var = var;
-        v.pert.index = idx;
-        v.pert.delta = delta;
-        v.err = err;
-        v.errval = errval;
-        vs.push_back(v);
-    };
-    addv(-1, 0, 0.0, -1, 0.0);
-    for (int q = 0; q < np; ++q) addv(1, q, P0.eps, -1, 0.0);
-    for (int q = 0; q < na; ++q) addv(2, q, P0.eps, -1, 0.0);
-    UP.off_x2 = (int)vs.size();
-    if (ne > 0) {
-        for (int q = 0; q < np; ++q) addv(1, q, P0.eps2, -1, 0.0);
-        for (int q = 0; q < na; ++q) addv(2, q, P0.eps2, -1, 0.0);
-    }
-    UP.off_err = (int)vs.size();
-    for (int e = 0; e < ne; ++e) {
-        addv(-1, 0, 0.0, e, P0.eps);
-        addv(-1, 0, 0.0, e, P0.eps2);
-        for (int q = 0; q < np; ++q) addv(1, q, P0.eps2, e, P0.eps2);
-        for (int q = 0; q < na; ++q) addv(2, q, P0.eps2, e, P0.eps2);
-    }
-    return vs;
-}
-
 // The assembly problem and buffers of the ud workspace (outputs packed in ud_out:
 // U_dx | U_dx_add | U_derr | U_derr_dx | U_derr_dx_add); returns the variant list.
 static std::vector<grape::VSpec> ud_setup(grape_plan *p, grape_unitary::UProblem &UP, grape_unitary::UBuffers &UB) {
@@ -2714,14 +2616,16 @@ static std::vector<grape::VSpec> ud_setup(grape_plan *p, grape_unitary::UProblem
     const int D = P0.D, Nt = P0.Nt, np = P0.np, na = P0.na, ne = P0.ne;
     const size_t T = (size_t)D * D;
     UP = grape_unitary::UProblem{};
-    std::vector<grape::VSpec> vs = ud_variants(P0, UP);
+    grape_setup::Variants V = ud_variants(P0);
+    UP.off_x2 = V.off_dx2;
+    UP.off_err = V.off_err;
     UP.D = D;
     UP.Nt = Nt;
     UP.np = np;
     UP.na = na;
     UP.ne = ne;
-    UP.nv = (int)vs.size();
-    UP.nslots = np + na + ne + ne * (np + na);
+    UP.nv = (int)V.vs.size();
+    UP.nslots = ud_nslots(P0);
     UP.inv_eps = P0.inv_eps;
     UP.inv_eps2sq = 1.0 / (P0.eps2 * P0.eps2);
     UP.gscr = p->ud_gscr;
@@ -2738,7 +2642,7 @@ static std::vector<grape::VSpec> ud_setup(grape_plan *p, grape_unitary::UProblem
     UB.Ue = UB.Udxa + n_dxa;
     UB.Uedx = UB.Ue + n_e;
     UB.Uedxa = UB.Uedx + n_edx;
-    return vs;
+    return std::move(V.vs);
 }
 
 static int unitary_derivs(grape_plan *p, const double *x, const double *Htab, double *U, double *U_dx,
@@ -2796,16 +2700,11 @@ static int dense_expm_batch(int device, int ndim, int n, const double *A, double
     const size_t IMG = grape_dense::kImgDoubles;
     std::vector<double> h((size_t)n * IMG);
     for (int i = 0; i < n; ++i) to_dense_image(A + 2 * (size_t)i * ndim * ndim, ndim, h.data() + i * IMG);
+    grape_setup::DevicePool mem;
     double *dA = nullptr, *dE = nullptr;
     int *dctrl = nullptr;
-    auto cleanup = [&]() {
-        (void)hipFree(dA); (void)hipFree(dE); (void)hipFree(dctrl);
-    };
-    if (dalloc(&dA, n * IMG) || dalloc(&dE, n * IMG) || dalloc(&dctrl, 8)) {
-        cleanup();
+    if (mem.alloc(&dA, n * IMG) || mem.alloc(&dE, n * IMG) || mem.alloc(&dctrl, 8))
         return fail(GRAPE_ERR_ALLOC, "device allocation failed");
-    }
-    int rc = GRAPE_OK;
     int ctrl[8] = {0};
     if (grape_dense::set_lds_limits() != hipSuccess ||
         hipMemcpy(dA, h.data(), h.size() * sizeof(double), hipMemcpyHostToDevice) != hipSuccess ||
@@ -2814,9 +2713,7 @@ static int dense_expm_batch(int device, int ndim, int n, const double *A, double
         hipDeviceSynchronize() != hipSuccess ||
         hipMemcpy(h.data(), dE, h.size() * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess ||
         hipMemcpy(ctrl, dctrl, 8 * sizeof(int), hipMemcpyDeviceToHost) != hipSuccess)
-        rc = fail(GRAPE_ERR_HIP, std::string("dense expm batch failed: ") + hipGetErrorString(hipGetLastError()));
-    cleanup();
-    if (rc) return rc;
+        return fail(GRAPE_ERR_HIP, std::string("dense expm batch failed: ") + hipGetErrorString(hipGetLastError()));
     for (int i = 0; i < n; ++i) from_dense_image(h.data() + i * IMG, ndim, E + 2 * (size_t)i * ndim * ndim);
     if (stats)
         for (int k = 0; k < 5; ++k) stats[k] = ctrl[2 + k];
@@ -2826,31 +2723,18 @@ static int dense_expm_batch(int device, int ndim, int n, const double *A, double
 
 static int expm_batch(int device, int ndim, int n, const double *A, double *E, int *stats, bool pivot) {
     if (ndim < 2 || ndim > GRAPE_MAX_DENSE_DIM) return fail(GRAPE_ERR_UNSUPPORTED, "ndim outside [2, GRAPE_MAX_DENSE_DIM]");
-    if (ndim > GRAPE_MAX_SMALL_DIM) {
-        if (n < 0 || (n > 0 && (!A || !E))) return fail(GRAPE_ERR_INVALID, "bad argument");
-        if (n == 0) return GRAPE_OK;
-        int ndev = 0;
-        if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return fail(GRAPE_ERR_NO_DEVICE, "no HIP device");
-        HIPCHECK(hipSetDevice(device));
-        return dense_expm_batch(device, ndim, n, A, E, stats, pivot);
-    }
     if (n < 0 || (n > 0 && (!A || !E))) return fail(GRAPE_ERR_INVALID, "bad argument");
     if (n == 0) return GRAPE_OK;
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return fail(GRAPE_ERR_NO_DEVICE, "no HIP device");
     HIPCHECK(hipSetDevice(device));
+    if (ndim > GRAPE_MAX_SMALL_DIM) return dense_expm_batch(device, ndim, n, A, E, stats, pivot);
     const size_t T = (size_t)ndim * ndim;
+    grape_setup::DevicePool mem;
     cd *dA = nullptr, *dE = nullptr;
     int *dovf = nullptr, *dctrl = nullptr;
-    auto cleanup = [&]() {
-        (void)hipFree(dA); (void)hipFree(dE); (void)hipFree(dovf); (void)hipFree(dctrl);
-    };
-    if (dalloc(&dA, n * T) || dalloc(&dE, n * T) || dalloc(&dovf, (size_t)n) ||
-        dalloc(&dctrl, 8)) {
-        cleanup();
+    if (mem.alloc(&dA, n * T) || mem.alloc(&dE, n * T) || mem.alloc(&dovf, (size_t)n) || mem.alloc(&dctrl, 8))
         return fail(GRAPE_ERR_ALLOC, "device allocation failed");
-    }
-    int rc = GRAPE_OK;
     int ctrl[8] = {0};
     if (hipMemcpy(dA, A, n * T * sizeof(cd), hipMemcpyHostToDevice) != hipSuccess ||
         hipMemset(dctrl, 0, 8 * sizeof(int)) != hipSuccess ||
@@ -2858,9 +2742,7 @@ static int expm_batch(int device, int ndim, int n, const double *A, double *E, i
         hipDeviceSynchronize() != hipSuccess ||
         hipMemcpy(E, dE, n * T * sizeof(cd), hipMemcpyDeviceToHost) != hipSuccess ||
         hipMemcpy(ctrl, dctrl, 8 * sizeof(int), hipMemcpyDeviceToHost) != hipSuccess)
-        rc = fail(GRAPE_ERR_HIP, std::string("expm batch failed: ") + hipGetErrorString(hipGetLastError()));
-    cleanup();
-    if (rc) return rc;
+        return fail(GRAPE_ERR_HIP, std::string("expm batch failed: ") + hipGetErrorString(hipGetLastError()));
     if (stats)
         for (int k = 0; k < 5; ++k) stats[k] = ctrl[2 + k];
     if (ctrl[1] & 1) return fail(GRAPE_ERR_SINGULAR, "singular Pade denominator");

@@ -62,7 +62,7 @@ struct DevProblem {
     int xadd_dep;        // H0 depends on x_add -> x_add FD variants exist
     int L, nchunks;      // scan chunking
     int scan_waves;      // waves per k_scan / k_err_scan workgroup (4 or 8)
-    // variant layout (see grape_engine.hip: build_variants)
+    // variant layout (see grape_plan_setup.hpp: build_variants)
     int off_dx, off_dxa, off_dx2, off_err, err_stride;
     int nvg, nz;         // gradient parameters (np + x_add when xadd_dep); local-frame slots per step (error path)
     double dt, eps, eps2, inv_eps, inv_eps2sq, DD, Dtr;

@@ -1,0 +1,94 @@
+"""The propagator-variant layout (robustgrape_amd/csrc/grape_plan_setup.hpp build_variants) on the host.
+
+The kernels index the list through off_dx / off_dxa / off_dx2 / off_err / err_stride, so a slip gives wrong
+gradients and no error.  tests/c/variants_check.cpp is built with hipcc (the types live in a header that
+includes HIP) as host code under AddressSanitizer and UBSan and run as an ordinary child process.
+
+The expected tables restate, by reading them, the three lists that plan construction wrote out by hand
+before the builder existed (grape_engine.hip at commit 5c26d4f):
+  * SMALL: grape_plan_create, l. 1322-1356 -- nxa = xadd_dep ? na : 0, eps-variants always;
+  * DENSE: create_dense, l. 1016-1048 -- the same nxa, every perturbed variant only when ne > 0;
+  * UD:    ud_variants, l. 2680-2708 -- nxa = na always, eps-variants always (it sets off_x2 = off_dx2 and
+           off_err only).
+eps = 1e-3, eps2 = 1e-2.
+"""
+import os
+import shutil
+import subprocess
+
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+E, E2 = 1e-3, 1e-2
+NOM = (-1, 0, 0.0, -1, 0.0)
+
+
+def X(q, d, e=-1, ev=0.0):  # control q perturbed by d (error source e at strength ev)
+    return (1, q, d, e, ev)
+
+
+def A(q, d, e=-1, ev=0.0):  # x_add q perturbed by d
+    return (2, q, d, e, ev)
+
+
+def ERR(e):  # the two unperturbed variants of error source e
+    return [(-1, 0, 0.0, e, E), (-1, 0, 0.0, e, E2)]
+
+
+# (np, nxa, ne, with_grad_variants) -> ((off_dx, off_dxa, off_dx2, off_err, err_stride), list)
+CASES = {
+    # (np, na, ne) = (1, 0, 0): SMALL and UD
+    (1, 0, 0, True): ((1, 2, 2, 2, 3), [NOM, X(0, E)]),
+    # ... DENSE: the nominal propagator alone
+    (1, 0, 0, False): ((1, 1, 1, 1, 3), [NOM]),
+    # (2, 1, 0) with xadd_dep: SMALL; UD with or without xadd_dep
+    (2, 1, 0, True): ((1, 3, 4, 4, 5), [NOM, X(0, E), X(1, E), A(0, E)]),
+    # ... DENSE
+    (2, 1, 0, False): ((1, 1, 1, 1, 5), [NOM]),
+    # (2, 1, 0) without xadd_dep: SMALL
+    (2, 0, 0, True): ((1, 3, 3, 3, 4), [NOM, X(0, E), X(1, E)]),
+    # ... DENSE
+    (2, 0, 0, False): ((1, 1, 1, 1, 4), [NOM]),
+    # (1, 1, 1) with xadd_dep: SMALL, DENSE (ne > 0) and UD
+    (1, 1, 1, True): ((1, 2, 3, 5, 4), [NOM, X(0, E), A(0, E), X(0, E2), A(0, E2)]
+                      + ERR(0) + [X(0, E2, 0, E2), A(0, E2, 0, E2)]),
+    # (2, 1, 2) without xadd_dep: SMALL and DENSE
+    (2, 0, 2, True): ((1, 3, 3, 5, 4), [NOM, X(0, E), X(1, E), X(0, E2), X(1, E2)]
+                      + ERR(0) + [X(0, E2, 0, E2), X(1, E2, 0, E2)]
+                      + ERR(1) + [X(0, E2, 1, E2), X(1, E2, 1, E2)]),
+    # ... UD (every x_add site)
+    (2, 1, 2, True): ((1, 3, 4, 7, 5), [NOM, X(0, E), X(1, E), A(0, E), X(0, E2), X(1, E2), A(0, E2)]
+                      + ERR(0) + [X(0, E2, 0, E2), X(1, E2, 0, E2), A(0, E2, 0, E2)]
+                      + ERR(1) + [X(0, E2, 1, E2), X(1, E2, 1, E2), A(0, E2, 1, E2)]),
+}
+
+
+@pytest.fixture(scope="module")
+def checker(tmp_path_factory):
+    if not os.path.exists(HIPCC) and not shutil.which("hipcc"):
+        pytest.skip("no hipcc")
+    exe = str(tmp_path_factory.mktemp("variants") / "variants_check")
+    subprocess.run([HIPCC, "-O1", "-std=c++17", "-Xarch_host", "-fsanitize=address,undefined",
+                    "-I" + os.path.join(ROOT, "robustgrape_amd", "csrc"), "-I" + os.path.join(ROOT, "include"),
+                    os.path.join(ROOT, "tests", "c", "variants_check.cpp"), "-o", exe], check=True, capture_output=True)
+    return exe
+
+
+@pytest.mark.parametrize("key", sorted(CASES), ids=lambda k: "np%d_nxa%d_ne%d_grad%d" % k)
+def test_variant_list_and_offsets(checker, key):
+    np_, nxa, ne, grad = key
+    offsets, want = CASES[key]
+    run = subprocess.run([checker] + [str(int(v)) for v in key], check=True, capture_output=True, text=True)
+    assert run.stderr == ""  # no sanitizer report
+    lines = [line.split() for line in run.stdout.splitlines()]
+    head = tuple(int(v) for v in lines[0])
+    got = [(int(a), int(b), float(c), int(d), float(e)) for a, b, c, d, e in lines[1:]]
+    assert got == want
+    assert head == (len(want),) + offsets
+    # the sizes the engines allocate by
+    grads = np_ + nxa if grad else 0
+    assert len(got) == 1 + grads + (np_ + nxa if ne > 0 else 0) + ne * (2 + np_ + nxa)
+    assert offsets[4] == 2 + np_ + nxa
+    if not grad:  # the dense engine without error sources
+        assert len(got) == 1 and offsets[:4] == (1, 1, 1, 1)
