@@ -216,6 +216,12 @@ typedef struct grape_desc {
  * both sector classes of an (evaluation, chunk) in one lane; this option launches
  * one walk kernel per class instead (the same chunking, the same results bit for bit). */
 #define GRAPE_OPT_NO_MERGE 32768
+/* Rank-one merged gradient walk (an addition within ABI 12: this option bit and grape_plan_rank1): with
+ * the diagonal head and exactly one projector-weighted level per sector, every sector block of M has
+ * one non-zero row, so the merged gradient walk carries two vectors per sector instead of a matrix
+ * state (the same quantity, other roundings).  This option keeps the matrix walk
+ * (grape_plan_rank1 tells which one a plan runs). */
+#define GRAPE_OPT_NO_RANK1 65536
 
 typedef struct grape_plan grape_plan;
 
@@ -499,6 +505,9 @@ int grape_plan_gauge_info(grape_plan *plan, int *gauge, int max_classes);
 /* 1 when every call of the plan runs one workgroup per evaluation (ABI 10; GRAPE_OPT_NO_EVAL1 above:
  * an eligible layout and max_batch <= 256), 0 otherwise, or a negative grape_status. */
 int grape_plan_eval1(grape_plan *plan);
+/* 1 when the plan's merged gradient walk is the rank-one one (GRAPE_OPT_NO_RANK1 above), 0
+ * otherwise (the matrix walk, or no merged walks), or a negative grape_status. */
+int grape_plan_rank1(grape_plan *plan);
 
 /*
  * Symmetry-adapted basis (ABI 8, host only: no device needed).  The unitary V (ndim x ndim,

@@ -1496,7 +1496,8 @@ static void walk_pair_order(const grape_plan *p, int *pa, int *pb) {
 // takes class A's chunking (fewer, longer chunks: its buffers, sized for its own count,
 // suffice) so that one lane can walk both (merged walks; GRAPE_OPT_NO_MERGE launches the
 // same chunking per class)
-static int setup_merge(grape_plan *p) {
+static int setup_merge(PlanBuild &b) {
+    grape_plan *p = b.p;
     if (p->ncls != 2) return GRAPE_OK;
     const DevProblem &P = p->P;
     int pa, pb;
@@ -1511,6 +1512,32 @@ static int setup_merge(grape_plan *p) {
     p->merge_pa = pa;
     for (int cl = 0; p->merged && cl < 2; ++cl)  // E~ of both classes for the merged walks' scalar loads
         if (int rc = fill_gauge_table(p, cl, false)) return rc;
+    // The rank-one gradient walk (grape_walk.hpp merged_step_grad_r1, GRAPE_OPT_NO_RANK1): the diagonal head
+    // writes row r of a sector's M block with the factor W[g_r] (grape_projector.hip diag_row, pass 1), so a
+    // sector with exactly one weighted level (the head's W and level order: the rotated ones with
+    // symmetry-adapted sectors) has M = e_c m^T.  Every sector of both classes must be such, and summed twins
+    // must hold that level at one in-sector index; anything else keeps the matrix walk.
+    const std::vector<double> &W = b.sps().W;
+    bool r1 = p->merged && p->SH.diag && !(P.opts & GRAPE_OPT_NO_RANK1);
+    for (int cl = 0; cl < 2; ++cl) {
+        const SectorClass &sc = b.ss.cls[cl];
+        DevProblem &Pc = p->Ps[cl];
+        Pc.rank1 = Pc.rank1_c[0] = Pc.rank1_c[1] = 0;
+        r1 = r1 && sc.nsec <= 2;
+        for (int w = 0; r1 && w < sc.nsec; ++w) {
+            int n = 0;
+            for (int r = 0; r < sc.S; ++r) {
+                const int g = sc.sidx[(size_t)w * sc.S + r];
+                if (g >= 0 && W[g] != 0.0) {
+                    Pc.rank1_c[w] = r;
+                    ++n;
+                }
+            }
+            r1 = r1 && n == 1;
+        }
+        if (Pc.twin && grape_walk::merged_twin_sum()) r1 = r1 && Pc.rank1_c[0] == Pc.rank1_c[1];
+    }
+    A.rank1 = Bq.rank1 = r1 ? 1 : 0;
     return GRAPE_OK;
 }
 
@@ -1573,7 +1600,7 @@ static int setup_sectors(PlanBuild &b) {
         H.MsecE[cl] = sb.MsecE;
     }
     p->ncls = (int)b.ss.cls.size();
-    if (int rc = setup_merge(p)) return rc;
+    if (int rc = setup_merge(b)) return rc;
     if (int rc = setup_eval1(p)) return rc;
     if (p->ncls == 2 && (hipStreamCreateWithFlags(&p->aux_stream, hipStreamNonBlocking) != hipSuccess ||
                          hipEventCreateWithFlags(&p->ev_fork, hipEventDisableTiming) != hipSuccess ||
@@ -1762,6 +1789,11 @@ int grape_plan_gauge_info(grape_plan *p, int *gauge, int max_classes) {
 int grape_plan_eval1(grape_plan *p) {
     if (!p) return fail(GRAPE_ERR_INVALID, "null plan");
     return p->e1 ? 1 : 0;
+}
+
+int grape_plan_rank1(grape_plan *p) {
+    if (!p) return fail(GRAPE_ERR_INVALID, "null plan");
+    return p->merged && p->Ps[0].rank1 && p->Ps[1].rank1 ? 1 : 0;
 }
 
 void grape_plan_destroy(grape_plan *plan) { free_plan(plan); }

@@ -115,6 +115,11 @@ struct DevProblem {
     // M_e = E~_e2 - E~ (k_gauge_err_base_fill)
     const cd *gauge_Et;
     int gauge_lab;
+    // Rank-one merged gradient walk (grape_walk.hpp merged_step_grad_r1): with the diagonal head and exactly one
+    // projector-weighted level per sector, every sector's M block is e_c m^T, so the walk carries two vectors
+    // per sector.  rank1_c[w]: that level's in-sector index c of sector w (launch-uniform; addresses only).
+    int rank1;
+    int rank1_c[2];
 };
 
 struct DevBatch {

@@ -1521,7 +1521,8 @@ __global__ __launch_bounds__(kWalkBlock, 1) void k_walk_grad_pair(DevProblem P0,
 // then fits in 120 VGPRs (four waves per SIMD: fwd 0.161 -> 0.145 ms per C2 pass); the gradient walk would
 // fit in 160 (three waves) but measured slower there (0.308 -> 0.322 ms: the per-step scalar loads sit on
 // its critical path), so it keeps E~ from LDS in registers at two waves (A/B in one GPU call,
-// profiles/r06/ab_smem).  0: E~ in LDS (gauge_base_lds).
+// profiles/r06/ab_smem).  0: E~ in LDS (gauge_base_lds).  That is the matrix gradient walk; the rank-one
+// one (merged_step_grad_r1) is small enough for the scalar loads to win at three waves (GRAPE_WALK_R1_ET_SMEM).
 #ifndef GRAPE_WALK_FWD_ET_SMEM
 #define GRAPE_WALK_FWD_ET_SMEM 1
 #endif
@@ -1937,6 +1938,124 @@ __device__ __forceinline__ double merged_step_grad(const cd *Et, const GaugeN<D>
     }
     return (kWalkPresum && NSEC > 1) ? tot : one;
 }
+// The rank-one gradient step (R1, DevProblem::rank1).  With the diagonal head every sector's M block has
+// one non-zero row, M = e_c m^T (grape_projector.hip diag_row: row r carries the factor W[g_r]), so
+//   X_k = Q_k M Q_k^dag = psi_k phi_k^dag,   psi_k = Q_k e_c,   phi_k = Q_k conj(m)
+// for the whole walk, and the matrix step's Y = X E^dag, X <- E Y are two matrix-vector products:
+//   phi <- E_k phi;   Y_jr = psi_j conj(phi_r);   psi <- E_k psi
+// -- the same quantity, no approximation.  The products u_rj = E_rj psi_j are taken once and serve both the
+// contraction (T_m from conj(phi_r) u_rj, grouped by charge difference as above) and psi <- sum_j u_rj.
+// Per 3-level sector and step: 36 FMA (phi) + 18 MUL + 18 FMA (u) + 24 FMA (T) + 12 ADD (psi), where the
+// matrix step spends 216 FMA on its two products and 24 on the contraction.
+// Its registers (24 VGPRs of state where the matrix walk holds 36, no Y) leave room for a third wave per SIMD once
+// E~ comes through scalar loads (GRAPE_WALK_R1_ET_SMEM: 108 VGPRs, no scratch; with E~ from LDS in registers the
+// lane spills at three waves), and there the scalar loads pay: C2 72.0-73.0 M evals/s at two waves with E~ from
+// LDS, 70.3-73.3 M at three (spilling), 77.9-78.3 M at three with scalar loads, 77.0-77.8 M at four (A/B in one GPU
+// call).  The matrix walk keeps GRAPE_WALK_MERGED_WAVES / GRAPE_WALK_GRAD_ET_SMEM.
+#ifndef GRAPE_WALK_R1_WAVES
+#define GRAPE_WALK_R1_WAVES 3
+#endif
+#ifndef GRAPE_WALK_R1_ET_SMEM
+#define GRAPE_WALK_R1_ET_SMEM 1
+#endif
+template <int D, int NE, int NSEC, bool LAD>
+__device__ __forceinline__ double merged_step_grad_r1(const cd *Et, const GaugeN<D> (&gn)[NE], cd p1, cd q,
+                                                      double inv_eps, cd (&psi)[NSEC][D], cd (&phi)[NSEC][D]) {
+    constexpr int NSH = NSEC / NE;
+    MStore<D, false> E[NE];
+#pragma unroll
+    for (int w = 0; w < NE; ++w) {
+        cd dph[kGaugePairs<D>];
+        if constexpr (LAD) gauge_phases_ladder<D>(p1, dph);
+        else gauge_phases<D>(p1, gn[w], dph);
+        gauge_prop_lds<D, GRAPE_WALK_R1_ET_SMEM>(Et + w * D * D, dph, E[w]);
+    }
+    cd rh[D];
+    if constexpr (LAD) ladder_rho<D>(q, rh);
+    double tot = 0.0, one = 0.0;
+#pragma unroll
+    for (int we = 0; we < NE; ++we) {
+        cd fw[kGaugePairs<D>];
+        if constexpr (!LAD) {
+#if GRAPE_GAUGE_FD_DN
+            gauge_fd_weights_dn<D>(q, gn[we], fw);
+#else
+            cd rho[D];
+#pragma unroll
+            for (int j = 0; j < D; ++j) rho[j] = gauge_rho(q, gn[we].n[j]);
+            gauge_fd_weights<D>(rho, fw);
+#endif
+        }
+#pragma unroll
+        for (int t = 0; t < NSH; ++t) {
+            const int w = we * NSH + t;
+            cd f[D], u[D][D];
+#pragma unroll
+            for (int r = 0; r < D; ++r) {  // phi <- E phi
+                cd c = czero();
+#pragma unroll
+                for (int j = 0; j < D; ++j) cmac(c, E[we].at(r, j), phi[w][j]);
+                f[r] = c;
+            }
+#pragma unroll
+            for (int r = 0; r < D; ++r) {
+                phi[w][r] = f[r];
+#pragma unroll
+                for (int j = 0; j < D; ++j) u[r][j] = cmulf(E[we].at(r, j), psi[w][j]);
+            }
+            double c = 0.0;
+            if constexpr (LAD) {  // T_m = sum_{r-j=m} conj(phi_r) u_rj + conj(sum_{r-j=-m} conj(phi_r) u_rj)
+                double tre[D], tim[D];
+#pragma unroll
+                for (int m = 0; m < D; ++m) tre[m] = tim[m] = 0.0;
+#pragma unroll
+                for (int r = 0; r < D; ++r) {
+#pragma unroll
+                    for (int j = 0; j < D; ++j) {
+                        if (r == j) continue;
+                        const int m = r > j ? r - j : j - r;
+                        tre[m] = fma(f[r].re, u[r][j].re, tre[m]);
+                        tre[m] = fma(f[r].im, u[r][j].im, tre[m]);
+                        if (r > j) {
+                            tim[m] = fma(f[r].re, u[r][j].im, tim[m]);
+                            tim[m] = fma(-f[r].im, u[r][j].re, tim[m]);
+                        } else {
+                            tim[m] = fma(-f[r].re, u[r][j].im, tim[m]);
+                            tim[m] = fma(f[r].im, u[r][j].re, tim[m]);
+                        }
+                    }
+                }
+#pragma unroll
+                for (int m = 1; m < D; ++m) {
+                    c = fma(rh[m].re, tre[m], c);
+                    c = fma(-rh[m].im, tim[m], c);
+                }
+            } else {  // sum_{r != j} Re(conj(phi_r) u_rj f_rj)
+#pragma unroll
+                for (int r = 0; r < D; ++r) {
+#pragma unroll
+                    for (int j = 0; j < D; ++j) {
+                        if (r == j) continue;
+                        const cd z = cmulf(cconj(f[r]), u[r][j]), g = gauge_fd_weight<D>(fw, r, j);
+                        c = fma(z.re, g.re, c);
+                        c = fma(-z.im, g.im, c);
+                    }
+                }
+            }
+            const double sv = c * inv_eps;
+            tot += sv;
+            one = sv;
+#pragma unroll
+            for (int r = 0; r < D; ++r) {  // psi <- E psi
+                cd s = u[r][0];
+#pragma unroll
+                for (int j = 1; j < D; ++j) s = cadd(s, u[r][j]);
+                psi[w][r] = s;
+            }
+        }
+    }
+    return (kWalkPresum && NSEC > 1) ? tot : one;
+}
 #ifndef GRAPE_WALK_TWIN_SUM  // merged gradient walk, twin class B: one summed state for both sectors
 #define GRAPE_WALK_TWIN_SUM 1
 #endif
@@ -1944,8 +2063,25 @@ __device__ __forceinline__ double merged_step_grad(const cd *Et, const GaugeN<D>
 #define GRAPE_WALK_MERGED_FDX 1
 #endif
 constexpr int kFdxTile = 16;  // steps per F_dx tile flush
-template <int DA, bool TWB, bool LAD>
-__global__ __launch_bounds__(kWalkBlock, GRAPE_WALK_MERGED_WAVES) void k_walk_grad_m(DevProblem PA, DevBatch BA,
+// the rank-one walk's chunk start of one sector: psi = Carry e_c, phi = Carry conj(m), m = row c of the sector's M
+// block (of the twins' summed block: Mw2).  c is launch-uniform and enters addresses only.
+template <int D>
+__device__ __forceinline__ void merged_r1_init(const cd *ca, size_t nbe, const cd *Mw, const cd *Mw2, int c,
+                                               cd (&psi)[D], cd (&phi)[D]) {
+    cd m[D];
+#pragma unroll
+    for (int e = 0; e < D; ++e) m[e] = cconj(Mw2 ? cadd(Mw[c * D + e], Mw2[c * D + e]) : Mw[c * D + e]);
+#pragma unroll
+    for (int j = 0; j < D; ++j) {
+        cd s = czero();
+#pragma unroll
+        for (int e = 0; e < D; ++e) cmac(s, ca[(size_t)(j * D + e) * nbe], m[e]);
+        phi[j] = s;
+        psi[j] = ca[(size_t)(j * D + c) * nbe];
+    }
+}
+template <int DA, bool TWB, bool LAD, bool R1>
+__global__ __launch_bounds__(kWalkBlock, (R1 ? GRAPE_WALK_R1_WAVES : GRAPE_WALK_MERGED_WAVES)) void k_walk_grad_m(DevProblem PA, DevBatch BA,
                                                                                    DevProblem PB, DevBatch BB, int a_first) {
     constexpr int NEB = TWB ? 1 : 2;
     __shared__ double ftile[kWalkBlock][kFdxTile + 1];  // (GRAPE_WALK_MERGED_FDX; +1: conflict-free rows)
@@ -1959,8 +2095,19 @@ __global__ __launch_bounds__(kWalkBlock, GRAPE_WALK_MERGED_WAVES) void k_walk_gr
     // the sectors' terms, so ONE state X = Carry (M_00 + M_11) Carry^dag carries both (GRAPE_WALK_TWIN_SUM:
     // half of class B's products; the sectors' sum formed once instead of per step -- rounding only)
     constexpr int NXB = (TWB && GRAPE_WALK_TWIN_SUM) ? 1 : 2;
-    cd XA[1][DA][DA], XB[NXB][2][2];
-    {  // carries lane-minor (k_scan_seq), the head's M blocks row-major per sub-evaluation
+    cd XA[1][DA][DA], XB[NXB][2][2];                          // the matrix walk's states
+    cd psiA[1][DA], phiA[1][DA], psiB[NXB][2], phiB[NXB][2];  // the rank-one walk's (R1: X = psi phi^dag)
+    if constexpr (R1) {
+        const size_t nbe = (size_t)L.nbe, be = (size_t)L.be;
+        merged_r1_init<DA>(BA.Carry + (size_t)L.c * DA * DA * nbe + be, nbe, BA.Msec + be * DA * DA, nullptr, PA.rank1_c[0],
+                           psiA[0], phiA[0]);
+#pragma unroll
+        for (int w = 0; w < NXB; ++w) {  // (twin sum: m = m_0 + m_1, both sectors' level at one index)
+            const cd *mb = BB.Msec + (be * 2 + w) * 4;
+            merged_r1_init<2>(BB.Carry + ((size_t)(TWB ? 0 : w) * PB.nchunks + L.c) * 4 * nbe + be, nbe, mb,
+                              NXB == 1 ? mb + 4 : nullptr, PB.rank1_c[w], psiB[w], phiB[w]);
+        }
+    } else {  // carries lane-minor (k_scan_seq), the head's M blocks row-major per sub-evaluation
         const size_t nbe = (size_t)L.nbe, be = (size_t)L.be;
         cd Cr[DA * DA];
         const cd *ca = BA.Carry + (size_t)L.c * DA * DA * nbe + be;
@@ -1980,10 +2127,11 @@ __global__ __launch_bounds__(kWalkBlock, GRAPE_WALK_MERGED_WAVES) void k_walk_gr
             merged_xinit<2>(Cb, Mb, XB[w]);
         }
     }
-    const cd *EtA = GRAPE_WALK_GRAD_ET_SMEM
+    constexpr bool ET_SMEM = R1 ? GRAPE_WALK_R1_ET_SMEM : GRAPE_WALK_GRAD_ET_SMEM;
+    const cd *EtA = ET_SMEM
                         ? PA.gauge_Et
                         : gauge_base_lds<DA, 1>(PA, as_constant(PA.ops), BA.wscr + (size_t)L.slot * 2 * DA * DA);
-    const cd *EtB = GRAPE_WALK_GRAD_ET_SMEM
+    const cd *EtB = ET_SMEM
                         ? PB.gauge_Et
                         : gauge_base_lds<2, NEB>(PB, as_constant(PB.ops), BB.wscr + (size_t)L.slot * 2 * 2 * 4);
     GaugeN<DA> gA[1];
@@ -1998,8 +2146,14 @@ __global__ __launch_bounds__(kWalkBlock, GRAPE_WALK_MERGED_WAVES) void k_walk_gr
         const double xk = xn.v0, xe = xk + PA.eps;  // the reference's perturbed control
         xn = walk_load_x(1, xt + (size_t)min(k + 1, PA.Nt - 1) * xs, xs);  // next step's control
         const cd p1 = gauge_cis(PA.gauge_a * xk), q = cis_m1(PA.gauge_a * (xe - xk));  // (xe - xk: exact)
-        const double sa = merged_step_grad<DA, 1, 1, LAD>(EtA, gA, p1, q, PA.inv_eps, XA);
-        const double sb = merged_step_grad<2, NEB, NXB, LAD>(EtB, gB, p1, q, PB.inv_eps, XB);
+        double sa, sb;
+        if constexpr (R1) {
+            sa = merged_step_grad_r1<DA, 1, 1, LAD>(EtA, gA, p1, q, PA.inv_eps, psiA, phiA);
+            sb = merged_step_grad_r1<2, NEB, NXB, LAD>(EtB, gB, p1, q, PB.inv_eps, psiB, phiB);
+        } else {
+            sa = merged_step_grad<DA, 1, 1, LAD>(EtA, gA, p1, q, PA.inv_eps, XA);
+            sb = merged_step_grad<2, NEB, NXB, LAD>(EtB, gB, p1, q, PB.inv_eps, XB);
+        }
         double v = 0.0;  // k_sec_reduce's sum of the classes' parts, in the plan's class order
         v += a_first ? sa : sb;
         v += a_first ? sb : sa;
@@ -3203,153 +3357,5 @@ __global__ __launch_bounds__(kWalkBlock, err_lab_waves<D>()) void k_walk_err_lab
     }
 }
 
-
-// ---------------------------------------------------------------------------
-// The merged gradient walk in the gauge frame (round 6, GRAPE_WALK_GRAD_TILDE)
-// ---------------------------------------------------------------------------
-// k_walk_grad_m carries X_k = C M C^dag per class and forms E_k = D_k E~ D_k^dag in registers each step.
-// Here the state is X~ = D_k^dag X D_k (k_walk_err_lab's frame): per step
-//   Y~ = X~ E~^dag,  F_dx part = Re tr(Y~ (E~ o f)) / eps,  X~ <- Om (E~ Y~) Om^dag   (Om = D_{k+1}^dag D_k)
-// -- the same quantities (traces are frame-invariant), E~ a workgroup-uniform SGPR operand read row by row
-// (lab_rows), so E_k's registers and its formation go and the lane fits three waves per SIMD; the rotation
-// costs what E_k's formation did.  Ladder classes only (the merged walks' classes); output as k_walk_grad_m.
-// Measured slower and off: 168 VGPRs, three waves per SIMD, no scratch, parity-green (the gauge / walk /
-// parity suites on it), but 0.343 against 0.309-0.316 ms per C2 pass (A/B twice in one GPU call): the
-// row-wise uniform operands cost the products their cross-row ILP, which the third wave does not win back
-#ifndef GRAPE_WALK_GRAD_TILDE
-#define GRAPE_WALK_GRAD_TILDE 0
-#endif
-#ifndef GRAPE_WALK_GRAD_TILDE_WAVES
-#define GRAPE_WALK_GRAD_TILDE_WAVES 3
-#endif
-// sum_{r != j} Re(Y_jr (U o f)_rj) for ladder charges: f_rj = rho(r - j) (conj for r < j), grouped by charge
-// difference (merged_step_grad's contraction) with U uniform
-template <int D>
-__device__ __forceinline__ double lab_trace_ladder(const cd (&Y)[D][D], cptr<cd> U, const cd (&rh)[D]) {
-    double tre[D], tim[D];
-#pragma unroll
-    for (int m = 0; m < D; ++m) tre[m] = tim[m] = 0.0;
-    lab_rows<D>(U, Y[D - 1][D - 1].re, [&](int r, const cd (&u)[D]) {
-#pragma unroll
-        for (int j = 0; j < D; ++j) {
-            if (r == j) continue;
-            const int m = r > j ? r - j : j - r;
-            const cd y = Y[j][r], e = u[j];
-            tre[m] = fma(y.re, e.re, tre[m]);
-            tre[m] = fma(-y.im, e.im, tre[m]);
-            if (r > j) {
-                tim[m] = fma(y.re, e.im, tim[m]);
-                tim[m] = fma(y.im, e.re, tim[m]);
-            } else {
-                tim[m] = fma(-y.re, e.im, tim[m]);
-                tim[m] = fma(-y.im, e.re, tim[m]);
-            }
-        }
-#pragma unroll
-        for (int m = 1; m < D; ++m) asm volatile("" : "+v"(tre[m]), "+v"(tim[m]));
-        return tre[D - 1];
-    });
-    double c = 0.0;
-#pragma unroll
-    for (int m = 1; m < D; ++m) {
-        c = fma(rh[m].re, tre[m], c);
-        c = fma(-rh[m].im, tim[m], c);
-    }
-    return c;
-}
-template <int D>
-__device__ __forceinline__ double tilde_step(cptr<cd> Et, const cd (&om_e)[kGaugePairs<D>], const cd (&rh)[D],
-                                             cd (&X)[D][D]) {
-    cd Y[D][D];
-    lab_mul_udag<D, false>(X, Et, Y);            // Y~ = X~ E~^dag
-    const double s = lab_trace_ladder<D>(Y, Et, rh);
-    lab_umul<D, false>(Et, Y, X);                // X~ = E~ Y~
-    lab_rotate<D>(om_e, X);                      // into the next step's frame
-    return s;
-}
-template <int DA, bool TWB>
-__global__ __launch_bounds__(kWalkBlock, GRAPE_WALK_GRAD_TILDE_WAVES) void k_walk_grad_mt(DevProblem PA, DevBatch BA,
-                                                                                       DevProblem PB, DevBatch BB, int a_first) {
-    constexpr int NXB = (TWB && GRAPE_WALK_TWIN_SUM) ? 1 : 2;
-    __shared__ double ftile[kWalkBlock][kFdxTile + 1];
-    __shared__ int2 frow[kWalkBlock];
-    const VBlock vb = hw_block();
-    const WalkLane L = walk_lane<1>(PA, BA, vb);
-    const double *xt = BA.xT + (size_t)L.be * (kWalkXRow ? PA.nx : 1);
-    const int xs = kWalkXRow ? 1 : L.nbe;
-    frow[threadIdx.x] = make_int2(L.ok ? L.be : -1, L.c * PA.L);
-    cd XA[DA][DA], XB[NXB][2][2];
-    {
-        const size_t nbe = (size_t)L.nbe, be = (size_t)L.be;
-        cd Cr[DA * DA];
-        const cd *ca = BA.Carry + (size_t)L.c * DA * DA * nbe + be;
-#pragma unroll
-        for (int e = 0; e < DA * DA; ++e) Cr[e] = ca[(size_t)e * nbe];
-        merged_xinit<DA>(Cr, BA.Msec + be * DA * DA, XA);
-#pragma unroll
-        for (int w = 0; w < NXB; ++w) {
-            cd Cb[4], Mb[4];
-            const cd *cb = BB.Carry + ((size_t)(TWB ? 0 : w) * PB.nchunks + L.c) * 4 * nbe + be;
-            const cd *mb = BB.Msec + (be * 2 + w) * 4;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                Cb[e] = cb[(size_t)e * nbe];
-                Mb[e] = NXB == 1 ? cadd(mb[e], mb[4 + e]) : mb[e];
-            }
-            merged_xinit<2>(Cb, Mb, XB[w]);
-        }
-    }
-    const int k0 = L.c * PA.L;
-    double xk = walk_load_x(1, xt + (size_t)min(k0, PA.Nt - 1) * xs, xs).v0;
-    {  // into the first step's frame: X~ = D_{k0}^dag X D_{k0}
-        const cd pc = cconj(gauge_cis(PA.gauge_a * xk));
-        cd ea[kGaugePairs<DA>], eb[kGaugePairs<2>];
-        gauge_phases_ladder<DA>(pc, ea);
-        gauge_phases_ladder<2>(pc, eb);
-        lab_rotate<DA>(ea, XA);
-#pragma unroll
-        for (int w = 0; w < NXB; ++w) lab_rotate<2>(eb, XB[w]);
-    }
-    const cptr<cd> gA0 = as_constant(PA.gauge_Et), gB0 = as_constant(PB.gauge_Et);
-    auto step = [&](int jj) {
-        const int k = min(k0 + jj, PA.Nt - 1);
-        const double xn = walk_load_x(1, xt + (size_t)min(k + 1, PA.Nt - 1) * xs, xs).v0;
-        const double xe = xk + PA.eps;  // the reference's perturbed control
-        const cd q = cis_m1(PA.gauge_a * (xe - xk)), om = gauge_cis(PA.gauge_a * xk - PA.gauge_a * xn);
-        xk = xn;
-        cptr<cd> gA = gA0, gB = gB0;  // (opaque per step: the row addresses stay in the step)
-        asm volatile("" : "+s"(gA), "+s"(gB));
-        cd rh[DA];
-        ladder_rho<DA>(q, rh);
-        cd ea[kGaugePairs<DA>], eb[kGaugePairs<2>];
-        gauge_phases_ladder<DA>(om, ea);
-        gauge_phases_ladder<2>(om, eb);
-        cd rb[2];
-        rb[0] = rh[0];
-        rb[1] = rh[1];
-        const double sa = tilde_step<DA>(gA, ea, rh, XA) * PA.inv_eps;
-        double sb = 0.0;
-#pragma unroll
-        for (int w = 0; w < NXB; ++w) sb += tilde_step<2>(gB + (TWB ? 0 : w) * 4, eb, rb, XB[w]) * PB.inv_eps;
-        double v = 0.0;  // k_sec_reduce's sum of the classes' parts, in the plan's class order
-        v += a_first ? sa : sb;
-        v += a_first ? sb : sa;
-        return v;
-    };
-#pragma unroll 1
-    for (int j0 = 0; j0 < PA.L; j0 += kFdxTile) {
-        const int nj = min(kFdxTile, PA.L - j0);
-#pragma unroll 1
-        for (int t = 0; t < nj; ++t) ftile[threadIdx.x][t] = step(j0 + t);
-        __syncthreads();
-        const int j = threadIdx.x % kFdxTile;
-#pragma unroll 1
-        for (int row = threadIdx.x / kFdxTile; row < kWalkBlock; row += kWalkBlock / kFdxTile) {
-            const int br = frow[row].x, kk = frow[row].y + j0 + j;
-            if (j < nj && br >= 0 && kk < PA.Nt) BA.Fdx[(size_t)br * PA.nx + kk] = ftile[row][j];
-        }
-        __syncthreads();
-    }
-}
 
 }  // namespace grape

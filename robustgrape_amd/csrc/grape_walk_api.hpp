@@ -60,6 +60,8 @@ hipError_t launch_pair(int stage, const grape::DevProblem &P0, const grape::DevB
 bool merged_ok(const grape::DevProblem &PA, const grape::DevProblem &PB);
 // 1: the merged gradient walk writes F_dx rows itself (no k_sec_reduce for such passes)
 bool merged_writes_fdx();
+// 1: the merged gradient walk carries one summed state for a twin class's two sectors (GRAPE_WALK_TWIN_SUM)
+bool merged_twin_sum();
 // E~ of the class's nsec sectors into out [nsec][D][D] (DevProblem::gauge_Et; scr: 2 D^2 complex per sector)
 hipError_t fill_gauge_base(const grape::DevProblem &P, int nsec, grape::cd *scr, grape::cd *out, hipStream_t st);
 // the lab-frame error walks' base table [nsec][1 + 2 ne][D][D] (DevProblem::gauge_Et with gauge_lab; scr: 2 D^2

@@ -155,6 +155,7 @@ bool merged_ok(const grape::DevProblem &PA, const grape::DevProblem &PB) {
            PA.nvg == 1 && PB.nvg == 1 && PA.ne == 0 && PB.ne == 0;
 }
 bool merged_writes_fdx() { return GRAPE_WALK_MERGED_FDX != 0; }
+bool merged_twin_sum() { return GRAPE_WALK_TWIN_SUM != 0; }
 hipError_t fill_gauge_base(const grape::DevProblem &P, int nsec, grape::cd *scr, grape::cd *out, hipStream_t st) {
     if (nsec < 1 || nsec > 64) return hipErrorInvalidValue;
     switch (P.D) {
@@ -181,6 +182,8 @@ hipError_t launch_merged(int stage, const grape::DevProblem &PA, const grape::De
     if (!merged_ok(PA, PB)) return hipErrorInvalidValue;
     const long lanes = (long)BA.nb * PA.nchunks;  // (class A: one sector, BA.nb evaluations)
     const dim3 grid((unsigned)((lanes + grape::kWalkBlock - 1) / grape::kWalkBlock)), blk(grape::kWalkBlock);
+    // the rank-one gradient walk where the engine found every M block of rank one (DevProblem::rank1, both classes)
+    const bool r1 = PA.rank1 && PB.rank1;
     auto go = [&](auto da, auto tw, auto lad) {
         constexpr int DA = decltype(da)::value;
         constexpr bool TW = decltype(tw)::value;
@@ -190,10 +193,10 @@ hipError_t launch_merged(int stage, const grape::DevProblem &PA, const grape::De
         } else if (stage == 2) {  // the chunk-total scan (one lane per evaluation)
             hipLaunchKernelGGL((grape::k_scan_seq<DA, TW>), dim3((unsigned)((BA.nb + grape::kSeqBlock - 1) / grape::kSeqBlock)), dim3(grape::kSeqBlock), 0, st, PA,
                                BA, PB, BB, BA.nb);
-        } else if (GRAPE_WALK_GRAD_TILDE && LAD) {  // the gauge-frame gradient walk (ladder classes)
-            hipLaunchKernelGGL((grape::k_walk_grad_mt<DA, TW>), grid, blk, 0, st, PA, BA, PB, BB, a_first);
+        } else if (r1) {
+            hipLaunchKernelGGL((grape::k_walk_grad_m<DA, TW, LAD, true>), grid, blk, 0, st, PA, BA, PB, BB, a_first);
         } else {
-            hipLaunchKernelGGL((grape::k_walk_grad_m<DA, TW, LAD>), grid, blk, 0, st, PA, BA, PB, BB, a_first);
+            hipLaunchKernelGGL((grape::k_walk_grad_m<DA, TW, LAD, false>), grid, blk, 0, st, PA, BA, PB, BB, a_first);
         }
     };
     using I3 = std::integral_constant<int, 3>;

@@ -173,6 +173,7 @@ OPT_GRAPH_FORK = 4096  # accepted and ignored since round 5 (the captured fork w
 OPT_NO_GAUGE = 8192  # per-step exponentials even for phase-covariant walk classes (grape_walk.hpp GAUGE)
 OPT_NO_EVAL1 = 16384  # latency-bound calls through the pair-kernel pipeline, not one workgroup per evaluation
 OPT_NO_MERGE = 32768  # throughput passes: one walk kernel per sector class instead of merged lanes
+OPT_NO_RANK1 = 65536  # merged gradient walk: the 3x3 / 2x2 matrix state even where M's blocks are of rank one
 
 
 def _reserved(flags: int = 0, options: int = 0, scan_waves: int = 0):
