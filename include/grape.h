@@ -222,6 +222,15 @@ typedef struct grape_desc {
  * state (the same quantity, other roundings).  This option keeps the matrix walk
  * (grape_plan_rank1 tells which one a plan runs). */
 #define GRAPE_OPT_NO_RANK1 65536
+/* Wide pass (an addition within ABI 12: this option bit and grape_plan_wide): a plan whose merged gradient
+ * walk is the rank-one one serves device-resident calls (grape_fidelity_grad_device_async) of at least
+ * W = max_batch x (chunk count) evaluations in passes of W with one lane per evaluation over all N_t steps:
+ * a forward state walk, the head, a time-reversed gradient walk -- no time chunks, no chunk scan
+ * (N_t <= 4096).  What is left of a call below W, and every host-array entry, runs the chunked
+ * passes.  The path is chosen per call by count: the same x inside a wide pass and in a chunked one agrees to
+ * rounding (F 1e-12, F_dx 1e-11 max|F_dx| + 1e-13), not bit for bit; a repeated call repeats its bits.
+ * This option keeps the chunked passes for every call (grape_plan_wide tells W). */
+#define GRAPE_OPT_NO_WIDE 131072
 
 typedef struct grape_plan grape_plan;
 
@@ -508,6 +517,9 @@ int grape_plan_eval1(grape_plan *plan);
 /* 1 when the plan's merged gradient walk is the rank-one one (GRAPE_OPT_NO_RANK1 above), 0
  * otherwise (the matrix walk, or no merged walks), or a negative grape_status. */
 int grape_plan_rank1(grape_plan *plan);
+/* W, the evaluations of one wide pass (GRAPE_OPT_NO_WIDE above), 0 when the plan takes none, or a negative
+ * grape_status. */
+int grape_plan_wide(grape_plan *plan);
 
 /*
  * Symmetry-adapted basis (ABI 8, host only: no device needed).  The unitary V (ndim x ndim,

@@ -29,6 +29,7 @@ EXPORTED = ["grape_abi_version", "grape_build_id", "grape_last_error", "grape_in
             "grape_lbfgs_ls_end", "grape_lbfgs_step", "grape_robust_cost", "grape_slice_forward",
             "grape_slice_gradient", "grape_symmetry_basis", "grape_plan_sector_info", "grape_lbfgs_async_advance",
             "grape_slice_forward_device", "grape_slice_gradient_device", "grape_plan_gauge_info", "grape_plan_eval1", "grape_plan_rank1",
+            "grape_plan_wide",
             "grape_expm_batch_general"]
 KERNEL_NAMES = ["k_expm", "k_expm_high", "k_scan", "k_grad/k_err_local", "k_reduce_add", "k_err_scan", "k_err_grad",
                 "k_expm_grad", "k_grad_high", "k_dexp", "k_dscan", "k_dcarry", "k_dmc", "k_dgrad",
@@ -126,6 +127,8 @@ def lib():
         L.grape_plan_eval1.restype = ctypes.c_int
         L.grape_plan_rank1.argtypes = [vp]
         L.grape_plan_rank1.restype = ctypes.c_int
+        L.grape_plan_wide.argtypes = [vp]
+        L.grape_plan_wide.restype = ctypes.c_int
         L.grape_symmetry_basis.argtypes = [ctypes.POINTER(CDesc), dp, ctypes.POINTER(ctypes.c_int)]
         L.grape_symmetry_basis.restype = ctypes.c_int
         if L.grape_abi_version() != ABI_VERSION:

@@ -9,6 +9,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <climits>
 #include <cmath>
 #include <cstdio>
 #include <cstring>
@@ -238,6 +239,8 @@ struct grape_plan {
     // merge_pa: the index of the class of 3 or 4 levels
     bool merged = false;
     int merge_pa = 0;
+    // the wide pass (enqueue_wide): W = max_batch x nchunks evaluations per pass of a rank-one merged plan, or 0
+    int wide = 0;
     cd *d_e1_Et = nullptr, *d_e1_scr = nullptr;
     unsigned char *d_e1_tab = nullptr;  // the kernel's table blob (grape_eval1 tab_build)
     int e1_pa = 0;
@@ -1538,6 +1541,10 @@ static int setup_merge(PlanBuild &b) {
         if (Pc.twin && grape_walk::merged_twin_sum()) r1 = r1 && Pc.rank1_c[0] == Pc.rank1_c[1];
     }
     A.rank1 = Bq.rank1 = r1 ? 1 : 0;
+    // the wide pass: its U blocks and alphas take the chunk totals' and carries' buffers (alloc_class: at least
+    // max_batch x nchunks tiles per sector of either class, class B's sized for its own, larger, chunk count)
+    const long wide = (long)p->max_batch * A.nchunks;
+    if (r1 && !(P.opts & GRAPE_OPT_NO_WIDE) && grape_walk::wide_ok(A, Bq) && wide * 2 <= (long)INT_MAX) p->wide = (int)wide;
     return GRAPE_OK;
 }
 
@@ -1602,6 +1609,7 @@ static int setup_sectors(PlanBuild &b) {
     p->ncls = (int)b.ss.cls.size();
     if (int rc = setup_merge(b)) return rc;
     if (int rc = setup_eval1(p)) return rc;
+    if (p->e1) p->wide = 0;  // (one workgroup per evaluation serves every call of such a plan)
     if (p->ncls == 2 && (hipStreamCreateWithFlags(&p->aux_stream, hipStreamNonBlocking) != hipSuccess ||
                          hipEventCreateWithFlags(&p->ev_fork, hipEventDisableTiming) != hipSuccess ||
                          hipEventCreateWithFlags(&p->ev_join, hipEventDisableTiming) != hipSuccess))
@@ -1796,6 +1804,11 @@ int grape_plan_rank1(grape_plan *p) {
     return p->merged && p->Ps[0].rank1 && p->Ps[1].rank1 ? 1 : 0;
 }
 
+int grape_plan_wide(grape_plan *p) {
+    if (!p) return fail(GRAPE_ERR_INVALID, "null plan");
+    return p->wide;
+}
+
 void grape_plan_destroy(grape_plan *plan) { free_plan(plan); }
 
 void *grape_plan_stream(grape_plan *plan) { return plan ? (void *)plan->stream : nullptr; }
@@ -1869,10 +1882,7 @@ static grape_eval1::Args eval1_args(const grape_plan *p, const double *x, double
 
 // One launch sequence of `nb` evaluations on the plan's stream over workspace rows
 // [0, nb).  The caller copies the status word afterwards.
-static int enqueue(grape_plan *p, int nb, const double *d_x, double *d_F, double *d_Fdx, double *d_Fd2,
-                   double *d_Fd2dx) {
-    hipStream_t st = p->stream;
-    p->cur_stream = st;
+static KMark profiling_mark(grape_plan *p) {  // per-kernel event pairs on the stream being enqueued (profiling on)
     KMark mk;
     if (p->profiling) {
         mk.ctx = p;
@@ -1888,6 +1898,61 @@ static int enqueue(grape_plan *p, int nb, const double *d_x, double *d_F, double
             }
         };
     }
+    return mk;
+}
+
+// One wide pass (grape_walk_api.hpp launch_merged_wide) of nb == p->wide evaluations on the caller's buffers:
+// the forward state walk, the head (alpha per sector instead of the M blocks), the time-reversed gradient walk.
+// The U blocks and the alphas live in the chunk totals' and the carries' buffers, which hold exactly
+// max_batch x nchunks tiles per sector and are idle here (no chunks); later chunked passes follow in stream order.
+static int enqueue_wide(grape_plan *p, int nb, const double *d_x, double *d_F, double *d_Fdx) {
+    hipStream_t st = p->stream;
+    p->cur_stream = st;
+    const KMark mk = profiling_mark(p);
+    const int ma = p->merge_pa, mb = 1 - ma;
+    DevProblem Pw[2] = {p->Ps[ma], p->Ps[mb]};
+    DevBatch Bw[2]{};
+    grape_proj::SectorHead H = p->SH;
+    for (int i = 0; i < 2; ++i) {
+        const int cl = i == 0 ? ma : mb;
+        const grape_plan::SecBuf &sb = p->sb[cl];
+        Pw[i].nchunks = 1;
+        Pw[i].L = Pw[i].Nt;
+        Bw[i].nb = nb * Pw[i].nsec;
+        Bw[i].x = d_x;
+        Bw[i].xT = d_x;
+        Bw[i].F = d_F;
+        Bw[i].Fdx = d_Fdx;
+        Bw[i].Ub = sb.Tc;
+        Bw[i].Msec = sb.Carry;
+        Bw[i].status = p->d_ctrl + 2;
+        Bw[i].sink = p->d_sink;
+        H.Ub[cl] = sb.Tc;
+        H.Msec[cl] = sb.Carry;
+    }
+    H.alpha = 1;
+    H.x = d_x;
+    H.F = d_F;
+    H.Fdx = d_Fdx;
+    H.tgt_part = p->d_tgt_part;
+    const int a_first = ma == 0 ? 1 : 0;
+    mk(GRAPE_KERNEL_WALK_FWD, 0);
+    HIPCHECK(grape_walk::launch_merged_wide(0, Pw[0], Bw[0], Pw[1], Bw[1], a_first, st));
+    mk(GRAPE_KERNEL_WALK_FWD, 1);
+    mk(GRAPE_KERNEL_SCAN, 0);
+    HIPCHECK(grape_proj::launch_sector_head(H, nb, st));
+    mk(GRAPE_KERNEL_SCAN, 1);
+    mk(GRAPE_KERNEL_WALK_GRAD, 0);
+    HIPCHECK(grape_walk::launch_merged_wide(1, Pw[0], Bw[0], Pw[1], Bw[1], a_first, st));
+    mk(GRAPE_KERNEL_WALK_GRAD, 1);
+    return GRAPE_OK;
+}
+
+static int enqueue(grape_plan *p, int nb, const double *d_x, double *d_F, double *d_Fdx, double *d_Fd2,
+                   double *d_Fd2dx) {
+    hipStream_t st = p->stream;
+    p->cur_stream = st;
+    const KMark mk = profiling_mark(p);
     if (p->general_h0) return enqueue_general(p, nb, d_x, d_F, d_Fdx, d_Fd2, d_Fd2dx, mk);
     if (p->dense) {
         const grape_dense::DenseBatch DB = dense_batch(p, nb, d_x, d_F, d_Fdx, d_Fd2, d_Fd2dx);
@@ -2177,7 +2242,13 @@ int grape_fidelity_grad_device_async(grape_plan *p, int nbatch, const double *d_
     if (p->P.ne > 0 && nbatch > 0 && (!d_F_d2err || !d_F_d2err_dx))
         return fail(GRAPE_ERR_INVALID, "error sources need F_d2err and F_d2err_dx outputs");
     HIPCHECK(hipSetDevice(p->device));
-    for (int b0 = 0; b0 < nbatch; b0 += p->max_batch) {
+    // Device-resident batches of a rank-one merged plan: while at least W = max_batch x nchunks evaluations remain,
+    // one wide pass of W (one lane per evaluation, no chunks: enqueue_wide); the rest through the chunked passes.
+    // The path is chosen by count alone, so a repeated call repeats its bits.
+    int b0 = 0;
+    for (; p->wide > 0 && nbatch - b0 >= p->wide; b0 += p->wide)
+        if (int rc = enqueue_wide(p, p->wide, d_x + (size_t)b0 * p->P.nx, d_F + b0, d_F_dx + (size_t)b0 * p->P.nx)) return rc;
+    for (; b0 < nbatch; b0 += p->max_batch) {
         const int nb = std::min(p->max_batch, nbatch - b0);
         int rc = enqueue_call(p, nb, d_x + (size_t)b0 * p->P.nx, d_F + b0, d_F_dx + (size_t)b0 * p->P.nx,
                               p->P.ne ? d_F_d2err + (size_t)b0 * p->P.ne : nullptr,

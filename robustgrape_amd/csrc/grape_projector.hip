@@ -593,6 +593,14 @@ __device__ __forceinline__ void diag_row(const SectorHead &H, const DiagStage &S
             fsum += wr * pd(g[c]) * (K.re * K.re + K.im * K.im);
         }
         acc = p_add(acc, p_scale(wr, Kel(r, gr, r, gr)));
+    } else if (pass == 1 && H.alpha) {
+        // the wide pass (one weighted level c per sector): row c of M is alpha U_c. with
+        //   alpha = sc W_c conj(u0_c) (p_c conj(K_cc) + conj(tau))
+        // (the M row's two terms with U_ce factored out); the weighted row's lane writes it to Msec[b * ns + w]
+        if (gr < 0 || St.W[gr] == 0.0) return;
+        const cd kc = p_conj(Kel(r, gr, r, gr));
+        const cd f = p_add(p_scale(pd(gr), kc), cd{tau.re, -tau.im});
+        H.Msec[cl][b * ns + w] = p_scale(sc, p_scale(St.W[gr], p_mul(p_conj(u0[gr]), f)));
     } else if (pass == 1) {
         cd *dst = H.Msec[cl] + (b * ns + w) * S * S + (size_t)r * S;
         cd Kr[S];  // column r of K

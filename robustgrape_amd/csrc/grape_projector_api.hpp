@@ -58,6 +58,9 @@ struct SectorHead {
     double *Fd2, *Fd2dx;
     int diag;                 // diagonal projector and target, sector classes of <= 4 levels: the
                               // fidelity head runs one thread per evaluation on the sector blocks
+    int alpha;                // diag, the wide pass (grape_walk_api.hpp launch_merged_wide): every sector has one
+                              // weighted level c and Ub holds column c only; instead of the M blocks the head
+                              // writes alpha per sector, Msec[c] = [nb * nsec], where row c of M is alpha U_c.
 };
 constexpr int kSectorLds = 2048;  // complex elements of LDS for the sector blocks M_ww (nsec * S * S)
 hipError_t launch_sector_head(const SectorHead &H, int nb, hipStream_t st);

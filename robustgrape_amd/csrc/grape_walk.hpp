@@ -1601,9 +1601,139 @@ constexpr int kFwdMUnroll = GRAPE_WALK_FWD_M_UNROLL;
 #ifndef GRAPE_WALK_FWD_M_WAVES  // the merged forward walk (120 VGPRs with E~ in SGPRs: four waves fit)
 #define GRAPE_WALK_FWD_M_WAVES 4
 #endif
+// ---------------------------------------------------------------------------
+// The wide pass (round 8): one lane per evaluation over all N_t steps, no time chunks
+// ---------------------------------------------------------------------------
+// The chunk totals, the carries and k_scan_seq exist because time is cut into chunks to fill the GPU at
+// max_batch evaluations per pass.  A device-resident call of at least W = max_batch x nchunks evaluations
+// fills the same lanes with one evaluation each, and a rank-one plan (DevProblem::rank1) then needs no S x S
+// chain at all: the diagonal head reads only U_cc of each sector and writes m = alpha U_c. (row c of M), so
+//   psi_N = U e_c (one vector, walked forward from e_c),   phi_N = conj(alpha) e_c (no walk),
+// and the gradient walk runs time-reversed from them, psi_{k-1} = E_k^dag psi_k (E_k = D_k E~ D_k^dag is
+// unitary: Hermitian H0), phi_{k-1} = E_k^dag phi_k, contracting conj(phi_k,r) (E_k)_rj psi_{k-1},j at every
+// step -- the chunked rank-one walk's quantity at the chunked walk's instruction count, 9 + 4 complex MACs per
+// forward step where the chain takes 27 + 4.  The recomputed psi_{k-1} carries the non-unitarity of the
+// computed E_k, about one rounding per step: the engine takes the wide pass up to N_t = 4096 only.
+// One launch per stage; the lane's chunk is the whole pulse (P.nchunks = 1, P.L = N_t in the launch's copies).
+struct WideLane {
+    int be, nbe;
+    bool ok;
+};
+__device__ __forceinline__ WideLane wide_lane(const DevBatch &BA) {  // (class A: one sector, BA.nb evaluations)
+    WideLane L;
+    const long g = (long)blockIdx.x * kWalkBlock + threadIdx.x;
+    L.nbe = BA.nb;
+    L.ok = g < (long)L.nbe;
+    L.be = L.ok ? (int)g : 0;  // lanes past the end walk evaluation 0 and store nothing
+    return L;
+}
+// psi <- E_k psi over NE propagators (merged_step_fwd's E formation, E~ through scalar loads)
+template <int D, int NE, bool LAD>
+__device__ __forceinline__ void wide_step_fwd(const cd *Et, const GaugeN<D> (&gn)[NE], cd p1, cd (&psi)[NE][D]) {
+#pragma unroll
+    for (int w = 0; w < NE; ++w) {
+        cd dph[kGaugePairs<D>];
+        if constexpr (LAD) gauge_phases_ladder<D>(p1, dph);
+        else gauge_phases<D>(p1, gn[w], dph);
+        MStore<D, false> E;
+        gauge_prop_lds<D, true>(Et + w * D * D, dph, E);
+        cd t[D];
+#pragma unroll
+        for (int j = 0; j < D; ++j) {
+            cd c = czero();
+#pragma unroll
+            for (int m = 0; m < D; ++m) cmac(c, psi[w][m], E.at(j, m));
+            t[j] = c;
+        }
+#pragma unroll
+        for (int j = 0; j < D; ++j) psi[w][j] = t[j];
+    }
+}
+// the head's U block of one sector from psi_N: column c filled, the rest zero (the head's sums weight every
+// other entry with zero, which must not meet a NaN)
+template <int D>
+__device__ __forceinline__ void wide_store_u(cd *u, int c, const cd (&psi)[D]) {
+#pragma unroll
+    for (int j = 0; j < D; ++j) {
+#pragma unroll
+        for (int i = 0; i < D; ++i) u[j * D + i] = i == c ? psi[j] : czero();
+    }
+}
+#ifndef GRAPE_WALK_WIDE_FWD_WAVES  // the wide forward walk (10 VGPRs of state)
+#define GRAPE_WALK_WIDE_FWD_WAVES 4
+#endif
+#ifndef GRAPE_WALK_WIDE_GRAD_WAVES  // the wide gradient walk
+#define GRAPE_WALK_WIDE_GRAD_WAVES 4
+#endif
+// The controls of the workgroup's kWalkBlock evaluations over one tile of kFdxTile steps, [row][step] in LDS:
+// sixteen lanes read one row's 128-byte piece per instruction, so every line of x is fetched once and used
+// whole.  (A lane streaming its own row touches one line per lane and step and finds it evicted eight steps
+// later at 262 144 lanes: the first cut of the wide walks fetched 4.8 GB per forward launch for 1.08 GB of
+// controls.)  The tile is loaded where it is needed: the other workgroups of the SIMD cover the one load latency
+// per kFdxTile steps, and a register copy of the next tile (16 values and their addresses per lane) cost the
+// gradient walk its fourth wave.  Rows past the last evaluation read the last one's.
+constexpr int kFdxTile = 16;  // steps per tile: the wide walks' x tiles, the merged gradient walks' F_dx flush
+__device__ __forceinline__ void wide_load_x(double (*tile)[kFdxTile + 1], const double *x, int nx, int nbe, int j0, int Nt) {
+    constexpr int kStep = kWalkBlock / kFdxTile;  // rows per instruction
+    const int j = threadIdx.x % kFdxTile, r0 = threadIdx.x / kFdxTile;
+    const double *xc = x + min(j0 + j, Nt - 1);
+    const long b0 = (long)blockIdx.x * kWalkBlock;
+#pragma unroll 4
+    for (int r = r0; r < kWalkBlock; r += kStep) tile[r][j] = xc[(size_t)min(b0 + r, (long)nbe - 1) * nx];
+}
 template <int DA, bool TWB, bool LAD>
-__global__ __launch_bounds__(kWalkBlock, GRAPE_WALK_FWD_M_WAVES) void k_walk_fwd_m(DevProblem PA, DevBatch BA,
+__device__ __forceinline__ void wide_fwd_body(const DevProblem &PA, const DevBatch &BA, const DevProblem &PB,
+                                              const DevBatch &BB) {
+    constexpr int NEB = TWB ? 1 : 2;
+    __shared__ double xtile[kWalkBlock][kFdxTile + 1];  // (+1: conflict-free rows)
+    const WideLane L = wide_lane(BA);
+    GaugeN<DA> gA[1];
+    GaugeN<2> gB[NEB];
+    gA[0] = gauge_charges<DA>(PA, 0);
+#pragma unroll
+    for (int w = 0; w < NEB; ++w) gB[w] = gauge_charges<2>(PB, w);
+    const int cA = PA.rank1_c[0];
+    cd psiA[1][DA], psiB[NEB][2];
+#pragma unroll
+    for (int j = 0; j < DA; ++j) psiA[0][j] = cmake(j == cA ? 1.0 : 0.0, 0.0);
+#pragma unroll
+    for (int w = 0; w < NEB; ++w) {
+#pragma unroll
+        for (int j = 0; j < 2; ++j) psiB[w][j] = cmake(j == PB.rank1_c[w] ? 1.0 : 0.0, 0.0);
+    }
+    auto step = [&](double xk) {
+        const cd p1 = gauge_cis(PA.gauge_a * xk);
+        wide_step_fwd<DA, 1, LAD>(PA.gauge_Et, gA, p1, psiA);
+        wide_step_fwd<2, NEB, LAD>(PB.gauge_Et, gB, p1, psiB);
+    };
+#pragma unroll 1
+    for (int j0 = 0; j0 < PA.Nt; j0 += kFdxTile) {
+        const int nj = min(kFdxTile, PA.Nt - j0);
+        wide_load_x(xtile, BA.x, PA.nx, L.nbe, j0, PA.Nt);
+        __syncthreads();
+        int t = 0;  // (unrolled by hand, as k_walk_fwd_m below)
+#pragma unroll 1
+        for (; t + 1 < nj; t += 2) {
+            step(xtile[threadIdx.x][t]);
+            step(xtile[threadIdx.x][t + 1]);
+        }
+        if (t < nj) step(xtile[threadIdx.x][t]);
+        __syncthreads();
+    }
+    if (L.ok) {
+        wide_store_u<DA>(BA.Ub + (size_t)L.be * DA * DA, cA, psiA[0]);
+#pragma unroll
+        for (int w = 0; w < 2; ++w)  // (twins: both sectors' U from the one chain)
+            wide_store_u<2>(BB.Ub + ((size_t)L.be * 2 + w) * 4, PB.rank1_c[w], psiB[TWB ? 0 : w]);
+    }
+}
+template <int DA, bool TWB, bool LAD, bool WIDE = false>
+__global__ __launch_bounds__(kWalkBlock, (WIDE ? GRAPE_WALK_WIDE_FWD_WAVES : GRAPE_WALK_FWD_M_WAVES)) void k_walk_fwd_m(DevProblem PA, DevBatch BA,
                                                                                   DevProblem PB, DevBatch BB) {
+    if constexpr (WIDE) {
+        wide_fwd_body<DA, TWB, LAD>(PA, BA, PB, BB);
+        return;
+    }
     constexpr int NEB = TWB ? 1 : 2;
     const VBlock vb = hw_block();
     const WalkLane L = walk_lane<1>(PA, BA, vb);  // (class A: one sector; its chunking is both classes')
@@ -2062,7 +2192,6 @@ __device__ __forceinline__ double merged_step_grad_r1(const cd *Et, const GaugeN
 #ifndef GRAPE_WALK_MERGED_FDX  // the merged gradient walk writes F_dx itself (1) or a part for k_sec_reduce (0)
 #define GRAPE_WALK_MERGED_FDX 1
 #endif
-constexpr int kFdxTile = 16;  // steps per F_dx tile flush
 // the rank-one walk's chunk start of one sector: psi = Carry e_c, phi = Carry conj(m), m = row c of the sector's M
 // block (of the twins' summed block: Mw2).  c is launch-uniform and enters addresses only.
 template <int D>
@@ -2080,12 +2209,181 @@ __device__ __forceinline__ void merged_r1_init(const cd *ca, size_t nbe, const c
         psi[j] = ca[(size_t)(j * D + c) * nbe];
     }
 }
-template <int DA, bool TWB, bool LAD, bool R1>
-__global__ __launch_bounds__(kWalkBlock, (R1 ? GRAPE_WALK_R1_WAVES : GRAPE_WALK_MERGED_WAVES)) void k_walk_grad_m(DevProblem PA, DevBatch BA,
+// One time-reversed gradient step of the wide pass, NSEC sectors over NE propagators: from psi_k and phi_k
+//   psi_{k-1} = E_k^dag psi_k;   v_rj = conj(phi_k,r) (E_k)_rj;   the step's term from v_rj psi_{k-1},j
+//   (grouped by charge difference with the rho weights and 1 / eps, as merged_step_grad_r1);
+//   phi_{k-1},j = conj(sum_r v_rj)
+// Per 3-level sector 36 FMA (psi) + 18 MUL + 18 FMA (v) + 24 FMA (T) + 12 ADD (phi): merged_step_grad_r1's count.
+template <int D, int NE, int NSEC, bool LAD>
+__device__ __forceinline__ double wide_step_grad(const cd *Et, const GaugeN<D> (&gn)[NE], cd p1, cd q, double inv_eps,
+                                                 cd (&psi)[NSEC][D], cd (&phi)[NSEC][D]) {
+    constexpr int NSH = NSEC / NE;
+    MStore<D, false> E[NE];
+#pragma unroll
+    for (int w = 0; w < NE; ++w) {
+        cd dph[kGaugePairs<D>];
+        if constexpr (LAD) gauge_phases_ladder<D>(p1, dph);
+        else gauge_phases<D>(p1, gn[w], dph);
+        gauge_prop_lds<D, true>(Et + w * D * D, dph, E[w]);
+    }
+    cd rh[D];
+    if constexpr (LAD) ladder_rho<D>(q, rh);
+    double tot = 0.0, one = 0.0;
+#pragma unroll
+    for (int we = 0; we < NE; ++we) {
+        cd fw[kGaugePairs<D>];
+        if constexpr (!LAD) {
+#if GRAPE_GAUGE_FD_DN
+            gauge_fd_weights_dn<D>(q, gn[we], fw);
+#else
+            cd rho[D];
+#pragma unroll
+            for (int j = 0; j < D; ++j) rho[j] = gauge_rho(q, gn[we].n[j]);
+            gauge_fd_weights<D>(rho, fw);
+#endif
+        }
+#pragma unroll
+        for (int t = 0; t < NSH; ++t) {
+            const int w = we * NSH + t;
+            cd pm[D], v[D][D];
+#pragma unroll
+            for (int j = 0; j < D; ++j) {  // psi_{k-1} = E^dag psi_k
+                cd s = czero();
+#pragma unroll
+                for (int r = 0; r < D; ++r) cmac(s, cconj(E[we].at(r, j)), psi[w][r]);
+                pm[j] = s;
+            }
+#pragma unroll
+            for (int r = 0; r < D; ++r) {
+#pragma unroll
+                for (int j = 0; j < D; ++j) v[r][j] = cmulf(cconj(phi[w][r]), E[we].at(r, j));
+            }
+            double c = 0.0;
+            if constexpr (LAD) {  // T_m = sum_{r-j=m} v_rj psi_j + conj(sum_{r-j=-m} v_rj psi_j)
+                double tre[D], tim[D];
+#pragma unroll
+                for (int m = 0; m < D; ++m) tre[m] = tim[m] = 0.0;
+#pragma unroll
+                for (int r = 0; r < D; ++r) {
+#pragma unroll
+                    for (int j = 0; j < D; ++j) {
+                        if (r == j) continue;
+                        const int m = r > j ? r - j : j - r;
+                        tre[m] = fma(v[r][j].re, pm[j].re, tre[m]);
+                        tre[m] = fma(-v[r][j].im, pm[j].im, tre[m]);
+                        if (r > j) {
+                            tim[m] = fma(v[r][j].re, pm[j].im, tim[m]);
+                            tim[m] = fma(v[r][j].im, pm[j].re, tim[m]);
+                        } else {
+                            tim[m] = fma(-v[r][j].re, pm[j].im, tim[m]);
+                            tim[m] = fma(-v[r][j].im, pm[j].re, tim[m]);
+                        }
+                    }
+                }
+#pragma unroll
+                for (int m = 1; m < D; ++m) {
+                    c = fma(rh[m].re, tre[m], c);
+                    c = fma(-rh[m].im, tim[m], c);
+                }
+            } else {  // sum_{r != j} Re(v_rj psi_j f_rj)
+#pragma unroll
+                for (int r = 0; r < D; ++r) {
+#pragma unroll
+                    for (int j = 0; j < D; ++j) {
+                        if (r == j) continue;
+                        const cd z = cmulf(v[r][j], pm[j]), g = gauge_fd_weight<D>(fw, r, j);
+                        c = fma(z.re, g.re, c);
+                        c = fma(-z.im, g.im, c);
+                    }
+                }
+            }
+            const double sv = c * inv_eps;
+            tot += sv;
+            one = sv;
+#pragma unroll
+            for (int j = 0; j < D; ++j) {  // phi_{k-1} = E^dag phi_k = conj of the column sums of v
+                cd s = v[0][j];
+#pragma unroll
+                for (int r = 1; r < D; ++r) s = cadd(s, v[r][j]);
+                phi[w][j] = cconj(s);
+                psi[w][j] = pm[j];
+            }
+        }
+    }
+    return (kWalkPresum && NSEC > 1) ? tot : one;
+}
+// the wide gradient walk's start of one sector: psi_N = column c of the head's U block, phi_N = conj(alpha) e_c
+// (alpha: the head's factor of row c of M, grape_projector.hip diag_row; summed over a twin pair: a2)
+template <int D>
+__device__ __forceinline__ void wide_grad_init(const cd *u, const cd *a, const cd *a2, int c, cd (&psi)[D], cd (&phi)[D]) {
+    const cd al = cconj(a2 ? cadd(*a, *a2) : *a);
+#pragma unroll
+    for (int j = 0; j < D; ++j) {
+        psi[j] = u[j * D + c];
+        phi[j] = j == c ? al : czero();
+    }
+}
+template <int DA, bool TWB, bool LAD>
+__device__ __forceinline__ void wide_grad_body(const DevProblem &PA, const DevBatch &BA, const DevProblem &PB,
+                                               const DevBatch &BB, int a_first, double (*ftile)[kFdxTile + 1], int2 *frow) {
+    constexpr int NEB = TWB ? 1 : 2;
+    constexpr int NXB = (TWB && GRAPE_WALK_TWIN_SUM) ? 1 : 2;
+    const WideLane L = wide_lane(BA);
+    frow[threadIdx.x] = make_int2(L.ok ? L.be : -1, 0);
+    cd psiA[1][DA], phiA[1][DA], psiB[NXB][2], phiB[NXB][2];
+    const size_t be = (size_t)L.be;
+    wide_grad_init<DA>(BA.Ub + be * DA * DA, BA.Msec + be, nullptr, PA.rank1_c[0], psiA[0], phiA[0]);
+#pragma unroll
+    for (int w = 0; w < NXB; ++w) {  // (twin sum: alpha_0 + alpha_1, both sectors' level at one index)
+        const cd *ab = BB.Msec + be * 2 + w;
+        wide_grad_init<2>(BB.Ub + (be * 2 + w) * 4, ab, NXB == 1 ? ab + 1 : nullptr, PB.rank1_c[w], psiB[w], phiB[w]);
+    }
+    GaugeN<DA> gA[1];
+    GaugeN<2> gB[NEB];
+    gA[0] = gauge_charges<DA>(PA, 0);
+#pragma unroll
+    for (int w = 0; w < NEB; ++w) gB[w] = gauge_charges<2>(PB, w);
+    auto step = [&](double xk) {  // one step of both classes: the F_dx value, in the plan's class order
+        const double xe = xk + PA.eps;
+        const cd p1 = gauge_cis(PA.gauge_a * xk), q = cis_m1(PA.gauge_a * (xe - xk));
+        const double sa = wide_step_grad<DA, 1, 1, LAD>(PA.gauge_Et, gA, p1, q, PA.inv_eps, psiA, phiA);
+        const double sb = wide_step_grad<2, NEB, NXB, LAD>(PB.gauge_Et, gB, p1, q, PB.inv_eps, psiB, phiB);
+        double v = 0.0;
+        v += a_first ? sa : sb;
+        v += a_first ? sb : sa;
+        return v;
+    };
+    // The tiles and the steps of a tile in descending order.  One workgroup tile serves both ways: it arrives
+    // holding the tile's controls (wide_load_x), each lane replaces x_k in its row by the step's F_dx value, and the
+    // flush writes the rows out as k_walk_grad_m's does (slot t of the tile is step j0 + t).
+    const int jlast = (PA.Nt - 1) / kFdxTile * kFdxTile;
+#pragma unroll 1
+    for (int j0 = jlast; j0 >= 0; j0 -= kFdxTile) {
+        const int nj = min(kFdxTile, PA.Nt - j0);
+        wide_load_x(ftile, BA.x, PA.nx, L.nbe, j0, PA.Nt);
+        __syncthreads();
+#pragma unroll 1
+        for (int t = nj - 1; t >= 0; --t) ftile[threadIdx.x][t] = step(ftile[threadIdx.x][t]);
+        __syncthreads();
+        const int j = threadIdx.x % kFdxTile;
+#pragma unroll 1
+        for (int row = threadIdx.x / kFdxTile; row < kWalkBlock; row += kWalkBlock / kFdxTile) {
+            const int br = frow[row].x;  // (br < 0: past the last lane)
+            if (j < nj && br >= 0) BA.Fdx[(size_t)br * PA.nx + j0 + j] = ftile[row][j];
+        }
+        __syncthreads();
+    }
+}
+template <int DA, bool TWB, bool LAD, bool R1, bool WIDE = false>
+__global__ __launch_bounds__(kWalkBlock, (WIDE ? GRAPE_WALK_WIDE_GRAD_WAVES : R1 ? GRAPE_WALK_R1_WAVES : GRAPE_WALK_MERGED_WAVES)) void k_walk_grad_m(DevProblem PA, DevBatch BA,
                                                                                    DevProblem PB, DevBatch BB, int a_first) {
     constexpr int NEB = TWB ? 1 : 2;
     __shared__ double ftile[kWalkBlock][kFdxTile + 1];  // (GRAPE_WALK_MERGED_FDX; +1: conflict-free rows)
     __shared__ int2 frow[kWalkBlock];                   // each row's evaluation and first step
+    if constexpr (WIDE) {
+        wide_grad_body<DA, TWB, LAD>(PA, BA, PB, BB, a_first, ftile, frow);
+        return;
+    }
     const VBlock vb = hw_block();
     const WalkLane L = walk_lane<1>(PA, BA, vb);
     const double *xt = BA.xT + (size_t)L.be * (kWalkXRow ? PA.nx : 1);

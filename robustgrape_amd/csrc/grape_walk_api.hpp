@@ -69,6 +69,16 @@ hipError_t fill_gauge_base(const grape::DevProblem &P, int nsec, grape::cd *scr,
 hipError_t fill_gauge_err_base(const grape::DevProblem &P, int nsec, grape::cd *scr, grape::cd *out, hipStream_t st);
 hipError_t launch_merged(int stage, const grape::DevProblem &PA, const grape::DevBatch &BA, const grape::DevProblem &PB,
                          const grape::DevBatch &BB, int a_first, hipStream_t st);
+// The wide pass of a rank-one merged plan (grape_walk.hpp, "The wide pass"): one lane per evaluation over all
+// N_t steps, BA.nb evaluations, no chunks and no scan.  Stage 0: k_walk_fwd_m<..., WIDE> walks psi = U e_c forward
+// and writes the head's U blocks (BA.Ub / BB.Ub: column c filled, the rest zero); stage 1: k_walk_grad_m<..., WIDE>
+// starts from them and the head's alpha per sector (BA.Msec / BB.Msec: [nb * nsec], SectorHead::alpha) and walks
+// back in time, writing the F_dx rows.  Both read BA.x ([nb][nx], no transposed copy) through workgroup tiles of
+// 16 steps.  wide_ok tells whether the classes fit.
+constexpr int kWideMaxNt = 4096;
+bool wide_ok(const grape::DevProblem &PA, const grape::DevProblem &PB);
+hipError_t launch_merged_wide(int stage, const grape::DevProblem &PA, const grape::DevBatch &BA, const grape::DevProblem &PB,
+                              const grape::DevBatch &BB, int a_first, hipStream_t st);
 // F_dx parts the class's gradient stage writes per evaluation: its sectors, or (k_walk_grad with several
 // sectors per lane, no error sources) one pre-summed part per lane row (grape_walk.hpp kWalkPresum)
 int grad_parts(const grape::DevProblem &P);

@@ -208,6 +208,31 @@ hipError_t launch_merged(int stage, const grape::DevProblem &PA, const grape::De
         lad ? go(I3{}, std::false_type{}, std::true_type{}) : go(I3{}, std::false_type{}, std::false_type{});
     return hipGetLastError();
 }
+bool wide_ok(const grape::DevProblem &PA, const grape::DevProblem &PB) {
+    // rank-one plans with E~ tables; the lanes read x rows in place (GRAPE_WALK_XROW) and the gradient walk
+    // writes F_dx itself; N_t <= 4096: the recompute drift of psi is checked to there
+    return merged_ok(PA, PB) && PA.rank1 && PB.rank1 && PA.gauge_Et && PB.gauge_Et && grape::kWalkXRow &&
+           GRAPE_WALK_MERGED_FDX != 0 && PA.Nt <= kWideMaxNt;
+}
+hipError_t launch_merged_wide(int stage, const grape::DevProblem &PA, const grape::DevBatch &BA, const grape::DevProblem &PB,
+                              const grape::DevBatch &BB, int a_first, hipStream_t st) {
+    if (!wide_ok(PA, PB) || (stage != 0 && stage != 1)) return hipErrorInvalidValue;
+    const dim3 grid((unsigned)((BA.nb + grape::kWalkBlock - 1) / grape::kWalkBlock)), blk(grape::kWalkBlock);
+    auto go = [&](auto da, auto tw, auto lad) {
+        constexpr int DA = decltype(da)::value;
+        constexpr bool TW = decltype(tw)::value;
+        constexpr bool LAD = decltype(lad)::value;
+        if (stage == 0) hipLaunchKernelGGL((grape::k_walk_fwd_m<DA, TW, LAD, true>), grid, blk, 0, st, PA, BA, PB, BB);
+        else hipLaunchKernelGGL((grape::k_walk_grad_m<DA, TW, LAD, true, true>), grid, blk, 0, st, PA, BA, PB, BB, a_first);
+    };
+    using I3 = std::integral_constant<int, 3>;
+    const bool lad = PA.gauge_ladder && PB.gauge_ladder;
+    if (PB.twin)
+        lad ? go(I3{}, std::true_type{}, std::true_type{}) : go(I3{}, std::true_type{}, std::false_type{});
+    else
+        lad ? go(I3{}, std::false_type{}, std::true_type{}) : go(I3{}, std::false_type{}, std::false_type{});
+    return hipGetLastError();
+}
 
 // x [nb][nx] -> xT [nx][nb] through a 32 x 32 LDS tile (both sides coalesced)
 __global__ __launch_bounds__(256) void k_transpose_x(const double *x, double *xT, int nb, int nx) {

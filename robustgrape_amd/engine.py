@@ -267,7 +267,8 @@ class GrapePlan:
     def sector_info(self) -> dict:
         """{"twin": (per class: its two sectors share one exponential per step), "symmetric":
         the sectors are the symmetry-adapted ones, "rank1": the merged gradient walk is the rank-one
-        one (grape_plan_rank1)} (include/grape.h grape_plan_sector_info)."""
+        one (grape_plan_rank1), "wide": W, the evaluations of one wide pass of device-resident calls, or 0
+        (grape_plan_wide)} (include/grape.h grape_plan_sector_info)."""
         t, sym = (ctypes.c_int * 2)(), ctypes.c_int(0)
         k = _capi.lib().grape_plan_sector_info(self.handle, t, ctypes.byref(sym), 2)
         _capi.check(min(k, 0))
@@ -278,9 +279,11 @@ class GrapePlan:
         _capi.check(min(e1, 0))
         r1 = _capi.lib().grape_plan_rank1(self.handle)
         _capi.check(min(r1, 0))
+        wide = _capi.lib().grape_plan_wide(self.handle)
+        _capi.check(min(wide, 0))
         return {"twin": tuple(bool(t[c]) for c in range(k)), "symmetric": bool(sym.value),
                 "gauge": tuple(bool(g[c]) for c in range(kg)), "ladder": tuple(g[c] == 2 for c in range(kg)),
-                "eval1": bool(e1), "rank1": bool(r1)}
+                "eval1": bool(e1), "rank1": bool(r1), "wide": int(wide)}
 
 
 # Plan cache of the reference-shaped entry points (one plan per problem object, nparam and

@@ -174,6 +174,7 @@ OPT_NO_GAUGE = 8192  # per-step exponentials even for phase-covariant walk class
 OPT_NO_EVAL1 = 16384  # latency-bound calls through the pair-kernel pipeline, not one workgroup per evaluation
 OPT_NO_MERGE = 32768  # throughput passes: one walk kernel per sector class instead of merged lanes
 OPT_NO_RANK1 = 65536  # merged gradient walk: the 3x3 / 2x2 matrix state even where M's blocks are of rank one
+OPT_NO_WIDE = 131072  # device-resident calls of rank-one plans: the chunked passes at every count (no wide pass)
 
 
 def _reserved(flags: int = 0, options: int = 0, scan_waves: int = 0):
