@@ -27,11 +27,9 @@ WALK = os.path.join(CSRC, "grape_walk_inst.hip")
 EVAL1 = os.path.join(CSRC, "grape_eval1.hip")
 DIMS = list(range(2, 13))  # GRAPE_DIMS in grape_launch.hpp; GRAPE_MAX_SMALL_DIM = 12
 SOURCES = [ENGINE, INST, DENSE, UNITARY, LBFGS, PROJ, WALK, EVAL1]
-DEPS = SOURCES + [os.path.join(CSRC, f) for f in
-                  ("grape_device.hpp", "grape_kernels.hpp", "grape_errpath.hpp", "grape_launch.hpp", "grape_lane.hpp",
-                   "grape_walk.hpp", "grape_walk_api.hpp", "grape_eval1_api.hpp",
-                   "grape_dense.hpp", "grape_dense_api.hpp", "grape_unitary_api.hpp",
-                   "grape_projector_api.hpp", "grape_plan_setup.hpp")] + \
+# every source and header of the library (an #include of a file that is not here would not reach source_id():
+# tests/test_capi_cpu.py checks the includes), the C ABI last
+DEPS = sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".hip", ".hpp"))) + \
     [os.path.join(ROOT, "include", "grape.h")]
 
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")

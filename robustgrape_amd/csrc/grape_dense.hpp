@@ -103,17 +103,11 @@ __device__ __forceinline__ SM sm_at(double *lds, int off) {
 // and the B-fragment reads of R^T were 2-way conflicted as ds_read2st64_b64 (C5's LDS conflict
 // cycles above its LDS-active cycles).  Checked exhaustively for every access pattern below by
 // scripts/probes/lds_banks.py.
-#ifndef GRAPE_DENSE_SWZ_R2  // 1: the round-2 swizzles (A/B)
-#define GRAPE_DENSE_SWZ_R2 0
-#endif
-__device__ __forceinline__ int swz64(int row) {
-    if (GRAPE_DENSE_SWZ_R2) return ((row & 15) << 1) ^ ((row & 1) << 4);
-    return (row & 15) | ((row & 1) << 4);
-}
+__device__ __forceinline__ int swz64(int row) { return (row & 15) | ((row & 1) << 4); }
 __device__ __forceinline__ int sidx(int row, int col) { return row * N + (col ^ swz64(row)); }
 // 64 x 16 / 16 x 16 buffers read as A fragments: conflict-free in both models with this swizzle (round 2:
 // row & 14, 2-way in the 16-lane one)
-__device__ __forceinline__ int sidx16(int row, int col) { return row * 16 + (col ^ (row & (GRAPE_DENSE_SWZ_R2 ? 14 : 15))); }
+__device__ __forceinline__ int sidx16(int row, int col) { return row * 16 + (col ^ (row & 15)); }
 
 __device__ __forceinline__ v4d mfma(double a, double b, v4d c) {
     return __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, c, 0, 0, 0);
@@ -245,16 +239,13 @@ struct Frag {
     double aR[2], aI[2], bR, bI;
 };
 
-// Round 6 (GRAPE_DENSE_FRAG_ADDR): the fragment addresses in closed form.  With the round-6 swizzle,
+// Round 6: the fragment addresses in closed form.  With the round-6 swizzle,
 // for k-step s (a compile-time constant in the unrolled loop) and byte offsets
 //   A of L:    a + ((32 s) ^ ac) (+ 8 192 for the second tile),   A of L^T: (a ^ (32 (s & 3) [+ 128])) + 2 048 s
 //   B of R^T:  b + ((32 s) ^ bc),                                  B of R:   (b ^ (32 (s & 3))) + 2 048 s
 // from four per-lane values formed once per product (frag_addr) -- one or two VALU instructions per address
 // and step, the rest the loads' immediate offsets, where recomputing sidx from the lane id cost ~15 per
 // step (checked for every lane, tile and step against sidx by scripts/probes/lds_banks.py).
-#ifndef GRAPE_DENSE_FRAG_ADDR
-#define GRAPE_DENSE_FRAG_ADDR 1
-#endif
 struct FragAddr {
     int a, ac, b, bc;
 };
@@ -284,14 +275,6 @@ __device__ __forceinline__ FragAddr frag_addr(const Lane &ln) {
 __device__ __forceinline__ double lds_at(const double *base, int byte_off) {
     return *reinterpret_cast<const double *>(reinterpret_cast<const char *>(base) + byte_off);
 }
-// GRAPE_DENSE_FA_BASE: both operands addressed from the LDS start, their regions' byte offsets folded
-// into fa.a / fa.b once per product.  Region 1 starts at 64 KB, beyond a ds_read_b64's 16-bit immediate:
-// addressed from its own base, every B (and, for L in region 1, A) fragment load of a step took two
-// v_add_u32 (base + re plane, base + im plane) and the re / im pair was not merged into one
-// ds_read2st64_b64.
-#ifndef GRAPE_DENSE_FA_BASE
-#define GRAPE_DENSE_FA_BASE 0
-#endif
 template <bool LT, bool RT, bool RC>
 __device__ __forceinline__ void mm_load_fa(SM L, SM R, int s, Frag &f, FragAddr &fa) {
     // made opaque in place at every step (no copies): each step's addresses are formed here instead of being
@@ -300,8 +283,8 @@ __device__ __forceinline__ void mm_load_fa(SM L, SM R, int s, Frag &f, FragAddr 
     else asm volatile("" : "+v"(fa.a), "+v"(fa.ac));
     if constexpr (RT) asm volatile("" : "+v"(fa.b), "+v"(fa.bc));
     else asm volatile("" : "+v"(fa.b));
-    const double *lre = GRAPE_DENSE_FA_BASE ? L.re - L.boff / 8 : L.re, *lim = lre + PLANE;
-    const double *rre = GRAPE_DENSE_FA_BASE ? R.re - R.boff / 8 : R.re, *rim = rre + PLANE;
+    const double *lre = L.re, *lim = lre + PLANE;
+    const double *rre = R.re, *rim = rre + PLANE;
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
         const int o = LT ? (fa.a ^ ((i ? 128 : 0) + 32 * (s & 3))) + 2048 * s : fa.a + ((32 * s) ^ fa.ac) + 8192 * i;
@@ -312,147 +295,48 @@ __device__ __forceinline__ void mm_load_fa(SM L, SM R, int s, Frag &f, FragAddr 
     f.bR = lds_at(rre, o);
     f.bI = RC ? -lds_at(rim, o) : lds_at(rim, o);
 }
-template <bool LT, bool RT, bool RC>
-__device__ __forceinline__ void mm_load(SM L, SM R, int s, Frag &f, const Lane &ln) {
-    // Indices are recomputed from a freshly pinned lane id every step: otherwise
-    // the compiler hoists all 16 steps' swizzled addresses of every product
-    // out of the enclosing loops and keeps them live (~100 VGPRs -> spills).
-    int l = ln.l;
-    asm volatile("" : "+v"(l));
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-        const int ir = 16 * ln.tile(i) + (l & 15), kc = 4 * s + (l >> 4);
-        const int o = LT ? sidx(kc, ir) : sidx(ir, kc);
-        f.aR[i] = L.re[o];
-        f.aI[i] = L.im[o];
-    }
-    const int kr = 4 * s + (l >> 4), jc = 16 * ln.w + (l & 15);
-    const int o = RT ? sidx(jc, kr) : sidx(kr, jc);
-    f.bR = R.re[o];
-    f.bI = RC ? -R.im[o] : R.im[o];
-}
-
 // Software-pipelined over the 16 k-steps: the fragments of step s+1 are loaded
-// while step s's 8 MFMAs issue; the "memory" pin stops the compiler from hoisting
+// while step s's 6 MFMAs issue; the "memory" fence stops the compiler from hoisting
 // every step's loads to the top (that costs ~100 VGPRs and forces spills).
 // Gauss's 3-multiplication complex product: 3 real MFMA streams per complex product instead
 // of 4; rounding-level differences only (the dense parity tests hold at T0).  Measured at C5:
 // 940 -> 1 064 evals/s, k_dgrad 0.52 -> 0.58 of the FP64 peak credited with the algorithmic
 // 8 d^3 per complex product (executed: 6 d^3).
-#ifndef GRAPE_DENSE_4M
-#define GRAPE_DENSE_4M 0
-#endif
-#ifndef GRAPE_DENSE_CONJ_EPI
-#define GRAPE_DENSE_CONJ_EPI 0
-#endif
-#ifndef GRAPE_DENSE_PINGPONG  // 3M products: fragment buffers by step parity (mm, below)
-#define GRAPE_DENSE_PINGPONG 1
-#endif
 template <bool LT, bool LC, bool RT, bool RC>
 __device__ __forceinline__ void mm(SM L, SM R, HM &P, const Lane &ln) {
-    if constexpr (GRAPE_DENSE_4M) {
-        // the conventional four real products: re += Lr Rr - Li Ri, im += Lr Ri + Li Rr
-        Frag fc, fn;
-        v4d tr[2], ti[2];
-#pragma unroll
-        for (int i = 0; i < 2; ++i) tr[i] = ti[i] = v4d{0.0, 0.0, 0.0, 0.0};
-        mm_load<LT, RT, RC>(L, R, 0, fc, ln);
-#pragma unroll
-        for (int s = 0; s < 16; ++s) {
-            if (s < 15) mm_load<LT, RT, RC>(L, R, s + 1, fn, ln);
-#pragma unroll
-            for (int i = 0; i < 2; ++i) {
-                const double ai = LC ? -fc.aI[i] : fc.aI[i];
-                tr[i] = mfma(fc.aR[i], fc.bR, tr[i]);
-                tr[i] = mfma(-ai, fc.bI, tr[i]);
-                ti[i] = mfma(fc.aR[i], fc.bI, ti[i]);
-                ti[i] = mfma(ai, fc.bR, ti[i]);
-            }
-            if (s < 15) {
-                fc = fn;
-                asm volatile("" : "+v"(fc.aR[0]), "+v"(fc.aR[1]), "+v"(fc.aI[0]), "+v"(fc.aI[1]), "+v"(fc.bR),
-                             "+v"(fc.bI)::"memory");
-            }
-        }
-#pragma unroll
-        for (int i = 0; i < 2; ++i) {
-            P.re[i] += tr[i];
-            P.im[i] += ti[i];
-        }
-        return;
-    }
     // Gauss's three-multiplication complex product: T1 = Lr Rr, T2 = Li Ri, T3 = (Lr + Li)(Rr + Ri),
     // P += (T1 - T2) + i (T3 - T1 - T2): 3 MFMAs per tile and k-step instead of 4.
-    // GRAPE_DENSE_CONJ_EPI: a conjugated operand's sign goes to the sums (a - b: a free source modifier)
-    // and to T2's sign in the combination below, instead of a negated copy of the fragment per step (two
-    // VALU instructions each: sign flip and move)
-    constexpr bool kCE = GRAPE_DENSE_CONJ_EPI;
-    constexpr bool kT2Neg = kCE && (LC != RC);  // T2 accumulated as -(Li Ri)
-    Frag fc, fn;
     v4d t1[2], t2[2], t3[2];
 #pragma unroll
     for (int i = 0; i < 2; ++i) t1[i] = t2[i] = t3[i] = v4d{0.0, 0.0, 0.0, 0.0};
-    constexpr bool kFA = GRAPE_DENSE_FRAG_ADDR && !GRAPE_DENSE_SWZ_R2;
-    FragAddr fa = kFA ? frag_addr<LT, RT>(pinned(ln)) : FragAddr{0, 0, 0, 0};
-    if constexpr (kFA && GRAPE_DENSE_FA_BASE) {
-        fa.a += L.boff;
-        fa.b += R.boff;
-    }
-    auto load = [&](int s, Frag &f) {
-        if constexpr (kFA) mm_load_fa<LT, RT, RC && !kCE>(L, R, s, f, fa);
-        else mm_load<LT, RT, RC && !kCE>(L, R, s, f, ln);
-    };
+    FragAddr fa = frag_addr<LT, RT>(pinned(ln));
+    auto load = [&](int s, Frag &f) { mm_load_fa<LT, RT, RC>(L, R, s, f, fa); };
     auto step = [&](const Frag &fc) {
-        const double bs = (kCE && RC) ? fc.bR - fc.bI : fc.bR + fc.bI;
+        const double bs = fc.bR + fc.bI;
 #pragma unroll
         for (int i = 0; i < 2; ++i) {
-            if constexpr (kCE) {
-                t1[i] = mfma(fc.aR[i], fc.bR, t1[i]);
-                t2[i] = mfma(fc.aI[i], fc.bI, t2[i]);
-                t3[i] = mfma(LC ? fc.aR[i] - fc.aI[i] : fc.aR[i] + fc.aI[i], bs, t3[i]);
-                continue;
-            }
             const double ai = LC ? -fc.aI[i] : fc.aI[i];
             t1[i] = mfma(fc.aR[i], fc.bR, t1[i]);
             t2[i] = mfma(ai, fc.bI, t2[i]);
             t3[i] = mfma(fc.aR[i] + ai, bs, t3[i]);
         }
     };
-    if constexpr (GRAPE_DENSE_PINGPONG) {
-        // two fragment buffers alternating by step parity (the loop is unrolled): no copy fc = fn, and
-        // the barrier between steps is a bare compiler fence (it keeps later steps' loads from being
-        // hoisted) instead of a pin on the fresh fragment, which forced the wait for step s+1's loads
-        // into step s after its first two MFMAs
-        Frag fb[2];
-        load(0, fb[0]);
-#pragma unroll
-        for (int s = 0; s < 16; ++s) {
-            if (s < 15) load(s + 1, fb[(s + 1) & 1]);
-            step(fb[s & 1]);
-            if (s < 15) asm volatile("" ::: "memory");
-        }
-    } else {
-    load(0, fc);
+    // two fragment buffers alternating by step parity (the loop is unrolled): no copy fc = fn, and
+    // the barrier between steps is a bare compiler fence (it keeps later steps' loads from being
+    // hoisted) instead of a pin on the fresh fragment, which forced the wait for step s+1's loads
+    // into step s after its first two MFMAs
+    Frag fb[2];
+    load(0, fb[0]);
 #pragma unroll
     for (int s = 0; s < 16; ++s) {
-        if (s < 15) load(s + 1, fn);
-        step(fc);
-        if (s < 15) {
-            fc = fn;
-            asm volatile("" : "+v"(fc.aR[0]), "+v"(fc.aR[1]), "+v"(fc.aI[0]), "+v"(fc.aI[1]), "+v"(fc.bR),
-                         "+v"(fc.bI)::"memory");
-        }
-    }
+        if (s < 15) load(s + 1, fb[(s + 1) & 1]);
+        step(fb[s & 1]);
+        if (s < 15) asm volatile("" ::: "memory");
     }
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
-        if constexpr (kT2Neg) {  // T2 = -t2: the same roundings as the negated-copy form
-            P.re[i] += t1[i] + t2[i];
-            P.im[i] += t3[i] - t1[i] + t2[i];
-        } else {
-            P.re[i] += t1[i] - t2[i];
-            P.im[i] += t3[i] - t1[i] - t2[i];
-        }
+        P.re[i] += t1[i] - t2[i];
+        P.im[i] += t3[i] - t1[i] - t2[i];
     }
 }
 
@@ -955,30 +839,15 @@ __device__ __forceinline__ void taylor_block(HM &x, int b, int n, const HM &A, c
 }
 
 // The Taylor degree for |A|_1 <= 0.95.  Paterson-Stockmeyer in A^4 costs 4 / 5 / 6 / 7 products at
-// degree 8 / 12 / 16 / 20 (degree 18 costs 7 as well).  GRAPE_DENSE_TAYLOR_U (default): the lowest of
-// them whose remainder bound |A|^(m+1) / (m+1)! is at most u = 2^-53, the accuracy Julia's theta_m
-// give its Pade degrees:  m = 8: |A|_1 <= 0.069,  12: <= 0.335,  16: <= 0.826,  20: <= 0.95 (bound
-// 6e-5 u there).  At C5 (|A|_1 in 0.49 .. 0.88) 98 % of the steps take degree 16.
-// GRAPE_DENSE_TAYLOR_U 0, GRAPE_DENSE_TAYLOR16 1: the bound of degree 18 at 0.95 (3.1e-18) for every
-// degree -- 8 <= 0.047, 12 <= 0.25, 16 <= 0.668, 18 above (64 % of C5's steps at degree 16).  Both 0:
-// round 2's 12 up to 0.25 and 18 above.
-#ifndef GRAPE_DENSE_TAYLOR16
-#define GRAPE_DENSE_TAYLOR16 1
-#endif
-#ifndef GRAPE_DENSE_TAYLOR_U
-#define GRAPE_DENSE_TAYLOR_U 1
-#endif
+// degree 8 / 12 / 16 / 20.  The lowest of them whose remainder bound |A|^(m+1) / (m+1)! is at most
+// u = 2^-53, the accuracy Julia's theta_m give its Pade degrees:  m = 8: |A|_1 <= 0.069,  12: <= 0.335,
+// 16: <= 0.826,  20: <= 0.95 (bound 6e-5 u there).  At C5 (|A|_1 in 0.49 .. 0.88) 98 % of the steps take
+// degree 16.  (The earlier degree tables, one bound of 3.1e-18 for every degree: DESIGN.md 7.)
 __device__ __forceinline__ int taylor_degree(double nA) {
-    if (GRAPE_DENSE_TAYLOR_U) {
-        if (nA <= 0.069) return 8;
-        if (nA <= 0.335) return 12;
-        if (nA <= 0.826) return 16;
-        return 20;
-    }
-    if (GRAPE_DENSE_TAYLOR16 && nA <= 0.047) return 8;
-    if (nA <= 0.25) return 12;
-    if (GRAPE_DENSE_TAYLOR16 && nA <= 0.668) return 16;
-    return 18;
+    if (nA <= 0.069) return 8;
+    if (nA <= 0.335) return 12;
+    if (nA <= 0.826) return 16;
+    return 20;
 }
 
 // A is in S0 and in registers; returns X = T(A).  Uses both LDS regions.

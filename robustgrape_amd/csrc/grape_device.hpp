@@ -579,7 +579,7 @@ __device__ __forceinline__ void pade_finish(Group<D> &G, const cd (&v)[D], const
 // degree 12: A^2, A^3 + 3 Horner steps = 5 (Pade 5: 3 + the LU solve); degree 6: 3.
 // Measured (C2, 16 384 evaluations per pass): k_expm_grad 41.5 -> 37.7 ms, C2
 // 748k -> 810k evals/s; C3 67.7k -> 76.1k (a Horner-in-A^2 variant with 6 products was
-// slower than Pade in k_expm_grad: 47.5 ms).  -DGRAPE_LOW_PADE=1 restores Pade 3 / 5.
+// slower than Pade in k_expm_grad: 47.5 ms).
 // ---------------------------------------------------------------------------
 __constant__ const double kInvFact[13] = {1.0, 1.0, 0.5, 1.0 / 6, 1.0 / 24, 1.0 / 120, 1.0 / 720,
                                           1.0 / 5040, 1.0 / 40320, 1.0 / 362880, 1.0 / 3628800,

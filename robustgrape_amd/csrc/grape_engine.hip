@@ -72,11 +72,7 @@ constexpr int kScanWide = grape_host::kScanWide, kScanNarrow = grape_host::kScan
 #endif
 constexpr int kForkMaxBatch = GRAPE_FORK_MAX_BATCH;
 // throughput passes of the Rydberg layout: both walk classes' one-wave scans in one launch
-// (grape_launch.hpp launch_scan_pair; GRAPE_SCAN_PAIR_ALL=0 keeps one launch per class for A/B)
-#ifndef GRAPE_SCAN_PAIR_ALL
-#define GRAPE_SCAN_PAIR_ALL 1
-#endif
-constexpr bool kScanPairAll = GRAPE_SCAN_PAIR_ALL;
+// (grape_launch.hpp launch_scan_pair)
 // chunks of a phase-covariant throughput walk class: (64 / S) / this per scan wave.  2: C2
 // 26.4 -> 29.0 M evals/s (4: 27.7 M; one GPU call, gpurun_out A/B r5chunk)
 #ifndef GRAPE_GAUGE_CHUNK_DIV
@@ -86,20 +82,11 @@ constexpr bool kScanPairAll = GRAPE_SCAN_PAIR_ALL;
 // C3).  C3 (A/B in one GPU call, profiles/r06/c3): 4-level class 8 -> 6 chunks 2.64 -> 2.68 M evals/s (12:
 // 2.49 M), 2-level class 16 -> 8 chunks 2.64 -> 2.69 M -- fewer lanes, whole waves per SIMD round, and
 // shorter error scans
-// latency-bound calls of the lab-frame error walks on the 16-wave scans (256 chunks of the 4-level class at
-// C3): measured slower, single C3 evaluation 0.169 -> 0.176 ms (A/B in one GPU call: the longer error scans
-// cost more than the shorter walks save), so off
-#ifndef GRAPE_LAB_LATENCY_SCAN
-#define GRAPE_LAB_LATENCY_SCAN 0
-#endif
 #ifndef GRAPE_LAB_CHUNKS4  // classes of 4 levels
 #define GRAPE_LAB_CHUNKS4 6
 #endif
 #ifndef GRAPE_LAB_CHUNKS2  // ... of fewer levels
 #define GRAPE_LAB_CHUNKS2 8
-#endif
-#ifndef GRAPE_GAUGE_CHUNK_DIV2  // ... for the 2-level classes (A/B knob)
-#define GRAPE_GAUGE_CHUNK_DIV2 GRAPE_GAUGE_CHUNK_DIV
 #endif
 // Chunk count of the 3-level phase-covariant class on throughput passes (the merged walks' chunking,
 // grape_walk.hpp k_walk_fwd_m / k_walk_grad_m).  A walk's time is (rounds of resident waves) x (steps
@@ -207,7 +194,6 @@ struct grape_plan {
     double *d_Fd2 = nullptr, *d_Fd2dx = nullptr, *d_part_err = nullptr;
     cd *d_Zl = nullptr;
     double *d_x = nullptr, *d_F = nullptr, *d_Fdx = nullptr, *d_part = nullptr, *d_tgt_part = nullptr;
-    double *d_xT = nullptr;  // chunk walks: the launch's controls transposed ([nx][nb])
     int *d_ovf = nullptr, *d_ctrl = nullptr;  // ctrl: [0], [1] overflow counts, [2] status
     // closure mode (GRAPE_DESC_HOST_TABLES): host-evaluated H and target tables
     bool tables = false;
@@ -1373,7 +1359,7 @@ static void decide_class(const PlanBuild &b, const SectorClass &sc, const std::v
     Ps.gauge_ladder = Ps.gauge;
     for (size_t i = 0; Ps.gauge && i < gauge_n.size(); ++i)
         if (gauge_n[i] != (int)(i % (size_t)S)) Ps.gauge_ladder = 0;
-    // error sources on a phase-covariant class: the lab-frame walks (no images, grape_walk.hpp
+    // error sources on a phase-covariant class: the lab-frame walks (no images, grape_walk.hpp,
     // GRAPE_WALK_ERR_LAB) when the base table's lanes fit one workgroup
     Ps.gauge_lab = (GRAPE_WALK_ERR_LAB && Ps.gauge && P.ne > 0 &&
                     sc.nsec * (1 + 2 * P.ne) <= grape::kLabBaseMaxLanes) ? 1 : 0;
@@ -1385,13 +1371,13 @@ static void decide_class(const PlanBuild &b, const SectorClass &sc, const std::v
                       !(P.opts & GRAPE_OPT_WALK_RECOMPUTE) ? 1 : 0;
     // latency-bound walk classes (fewer sub-evaluations than CUs, or the option): 16-wave scans,
     // half-length walks (grape_launch.hpp kScanLatency)
-    // (GRAPE_LAB_LATENCY_SCAN: the lab-frame error walks too)
-    if (Ps.walk && (P.ne == 0 || (Ps.gauge_lab && GRAPE_LAB_LATENCY_SCAN)) &&
+    // (not the error walks: the longer error scans cost more than the shorter walks save)
+    if (Ps.walk && P.ne == 0 &&
         (scan_override == kScanLatency || (scan_override == 0 && (long)R < (long)ncu)))
         Ps.scan_waves = kScanLatency;
     // phase-covariant throughput classes: a step costs a few products instead of an
     // exponential, so longer chunks (fewer per-lane prologues and a shorter scan) can pay
-    const int cdiv = (Ps.gauge && Ps.scan_waves == kScanTiny) ? (S == 2 ? GRAPE_GAUGE_CHUNK_DIV2 : GRAPE_GAUGE_CHUNK_DIV) : 1;
+    const int cdiv = (Ps.gauge && Ps.scan_waves == kScanTiny) ? GRAPE_GAUGE_CHUNK_DIV : 1;
     int ncs = std::max(1, std::min(Ps.scan_waves * (64 / S) / cdiv, P.Nt));
     if (Ps.gauge && Ps.scan_waves == kScanTiny && S == 3 && P.ne == 0)
         ncs = merged_chunk_count((long)MB, P.Nt, ncs, ncu);
@@ -1441,8 +1427,6 @@ static int alloc_class(PlanBuild &b, int cl, const std::vector<int> &gauge_n, co
     // stored propagators: D*D elements + the diagonal shift per (step, sector) (grape_walk.hpp kEwStride)
     if (Ps.walk_store_e && p->mem.alloc(&sb.Ew, (size_t)sc.nsec * Ps.L * (TS + 1) * lanes_pad) != hipSuccess)
         return fail(GRAPE_ERR_ALLOC, "device allocation failed (sector walks)");
-    if (Ps.walk && !p->d_xT && p->mem.alloc(&p->d_xT, MB * P.nx) != hipSuccess)
-        return fail(GRAPE_ERR_ALLOC, "device allocation failed (sector walks)");
     if (Ps.walk && (p->mem.alloc(&sb.Tc, R * Ps.nchunks * TS) != hipSuccess ||
                     p->mem.alloc(&sb.wscr, 2 * (size_t)sc.nsec * lanes_pad * TS) != hipSuccess))
         return fail(GRAPE_ERR_ALLOC, "device allocation failed (sector walks)");
@@ -1469,7 +1453,7 @@ static int alloc_class(PlanBuild &b, int cl, const std::vector<int> &gauge_n, co
 }
 
 // E~ of every sector of a phase-covariant class, once per plan, into sb[cl].gEt: the merged walks' table
-// (grape_walk.hpp GRAPE_WALK_ET_SMEM: the walks' own exponential, so the same bits as a per-workgroup
+// (grape_walk.hpp gauge_prop_lds: the walks' own exponential, so the same bits as a per-workgroup
 // copy) or, err: the lab-frame error walks' base table (1 + 2 ne matrices per sector).
 static int fill_gauge_table(grape_plan *p, int cl, bool err) {
     DevProblem &Pc = p->Ps[cl];
@@ -2005,7 +1989,7 @@ static int enqueue(grape_plan *p, int nb, const double *d_x, double *d_F, double
             B.Tc = sb.Tc;  // chunk walks (null otherwise)
             B.wscr = sb.wscr;
             B.Ew = sb.Ew;
-            B.xT = (nb == 1 || grape::kWalkXRow) ? d_x : p->d_xT;  // one evaluation: x[q] is already [nx][1]
+            B.xT = d_x;  // the walks read x rows in place
             sp.part[cl] = sb.part;
             sp.nsec[cl] = p->Ps[cl].walk ? grape_walk::grad_parts(p->Ps[cl]) : p->Ps[cl].nsec;
             if (p->merged && cl != p->merge_pa) sp.nsec[cl] = 0;  // (the merged walk's one part is class A's)
@@ -2016,11 +2000,6 @@ static int enqueue(grape_plan *p, int nb, const double *d_x, double *d_F, double
         bool parks = false;  // the chunk walks never park a step for k_expm_high: no counters to clear
         for (int cl = 0; cl < p->ncls; ++cl) parks = parks || !p->Ps[cl].walk;
         if (parks) HIPCHECK(hipMemsetAsync(p->d_ctrl + 4, 0, 4 * sizeof(int), st));
-        if (p->d_xT && nb > 1 && !grape::kWalkXRow) {  // the walks read the controls transposed (one coalesced row per step)
-            mk(GRAPE_KERNEL_WALK_FWD, 0);
-            HIPCHECK(grape_walk::transpose_x(d_x, p->d_xT, nb, p->P.nx, st));
-            mk(GRAPE_KERNEL_WALK_FWD, 1);
-        }
         // Small calls (latency-bound: the optimiser's line-search rounds, single evaluations) run
         // the second sector class on the auxiliary stream beside the first; large ones keep one
         // stream (no gain there, DESIGN 4.1, and per-kernel event times stay per kernel).
@@ -2060,7 +2039,7 @@ static int enqueue(grape_plan *p, int nb, const double *d_x, double *d_F, double
                 }
                 return e;
             }
-            if (s == 0 && !fork && !pair && kScanPairAll) {  // both walk classes' one-wave scans in one launch
+            if (s == 0 && !fork && !pair) {  // both walk classes' one-wave scans in one launch
                 const int ca = p->Ps[0].D == 2 ? 1 : 0, cb = 1 - ca;
                 const DevProblem &Pa = p->Ps[ca], &Pb = p->Ps[cb];
                 if (p->ncls == 2 && Pa.walk && Pb.walk && (Pa.D == 3 || Pa.D == 4) && Pb.D == 2 &&
@@ -2114,7 +2093,7 @@ static int enqueue(grape_plan *p, int nb, const double *d_x, double *d_F, double
             HIPCHECK(stage(2));
         }
         // (the merged gradient walk wrote F_dx itself; without x_add-dependent H0 nothing is left to sum)
-        if (!(p->merged && grape_walk::merged_writes_fdx() && !(p->P.xadd_dep && p->P.na > 0)))
+        if (!(p->merged && !(p->P.xadd_dep && p->P.na > 0)))
             HIPCHECK(dispatch_sector_reduce(p->Ps[0].D, p->Ps[0], Bc[0], sp, nb, st, mk));
         return GRAPE_OK;
     }

@@ -45,7 +45,7 @@ __global__ __launch_bounds__(64) void k_gauge_tilde(DevProblem P, cd *out, cd *s
     SM<D> A[1];
     walk_build<D, 1>(P, as_constant(P.ops) + (size_t)w * P.sec_ops, X0, 1, none, A);
     double mu0 = 0.0;
-    walk_expm<D, false, true, false>(A[0], scr + (size_t)w * 2 * D * D, mu0, true, [&](int i, const cd (&x)[D]) {
+    walk_expm<D, false, false>(A[0], scr + (size_t)w * 2 * D * D, mu0, true, [&](int i, const cd (&x)[D]) {
 #pragma unroll
         for (int j = 0; j < D; ++j) out[((size_t)w * D + j) * D + i] = x[j];
     });
@@ -292,14 +292,7 @@ __device__ __forceinline__ void lane_grad(const DevProblem &Pc, const cd *EtL, c
 #pragma unroll
         for (int e = 0; e < NE; ++e) {
             step_prop<D>(Et[e], gn[e], p1, E[e]);
-#if GRAPE_GAUGE_FD_DN
             gauge_fd_weights_dn<D>(q, gn[e], fwp[e]);
-#else
-            cd rho[D];
-#pragma unroll
-            for (int j = 0; j < D; ++j) rho[j] = gauge_rho(q, gn[e].n[j]);
-            gauge_fd_weights<D>(rho, fwp[e]);
-#endif
         }
 #pragma unroll
         for (int w = 0; w < NSEC; ++w) {  // Y = X E^dag, row by row

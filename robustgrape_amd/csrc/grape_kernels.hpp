@@ -154,7 +154,7 @@ struct DevBatch {
     cd *gp_scr;             // general projector: head scratch (grape_projector_api.hpp)
     double *sec_part;       // sectors: [nb][Nt][nvg] per-sector F_dx terms (k_sec_reduce sums them), else null;
                             // chunk walks: [nsec][Nt][nvg][nb / nsec], the evaluation fastest (coalesced)
-    const double *xT;       // chunk walks: the controls transposed, [nx][nb / nsec] (coalesced lane reads)
+    const double *xT;       // chunk walks: always equal to x (they read x rows in place; the field keeps the layout)
     const cd *Msec;         // sectors: [nb][D][D] the sector blocks of M = G U (the sector head)
     // sectors with error sources
     double *sec_part_err;   // [nb][ne][Nt][nvg] per-sector F_d2err_dx terms (k_sec_reduce_err sums them)
@@ -248,15 +248,8 @@ __device__ __forceinline__ void target_row(const DevProblem &P, const DevBatch &
 // instead of keeping A live through the Pade evaluation.
 constexpr int kCachedTerms = 6;
 
-// Low-norm regime (m in {3, 5}): the solve-free Taylor evaluation (grape_device.hpp,
-// default) or, built with -DGRAPE_LOW_PADE=1, Julia's Pade 3 / 5 with the LU solve.
-#if defined(GRAPE_LOW_PADE) && GRAPE_LOW_PADE
-#define EXPM_LOW(m_, ring_) expm_low<D>(G, (m_), a, x, valid, singular, rebuild)
-#define EXPM_GROUP_CD(D_) ::grape::Geo<D_>::GROUP_CD
-#else
-#define EXPM_LOW(m_, ring_) expm_taylor<D, (ring_)>(G, (m_), a, x, valid)
-#define EXPM_GROUP_CD(D_) ::grape::Geo<D_>::LEAN_CD
-#endif
+// Low-norm regime (m in {3, 5}): the solve-free Taylor evaluation (grape_device.hpp expm_taylor; the
+// groups take the lean LDS layout, Geo<D>::LEAN_CD: no LU workspace).
 #ifndef GRAPE_EXPM_GRAD_WAVES
 #define GRAPE_EXPM_GRAD_WAVES 3
 #endif
@@ -360,7 +353,7 @@ __global__ __launch_bounds__(64, (D <= 9 ? GRAPE_EXPM_WAVES_D9 : 2)) void k_expm
     constexpr int RING = ERR ? 2 : 3;  // LDS read ring of the products (mm_tile_ring)
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     cd *lds = reinterpret_cast<cd *>(smem_raw);
-    Group<D> G = make_group<D>(lds, threadIdx.x, EXPM_GROUP_CD(D));
+    Group<D> G = make_group<D>(lds, threadIdx.x, Geo<D>::LEAN_CD);
     const long nitems = (long)B.nb * P.Nt * P.nv;
     const long gid = (long)blockIdx.x * Geo<D>::GPW + G.g;
     const bool valid = G.lane_ok && gid < nitems;
@@ -373,19 +366,18 @@ __global__ __launch_bounds__(64, (D <= 9 ? GRAPE_EXPM_WAVES_D9 : 2)) void k_expm
                                       valid, b - bx * ns);
     cd a[D], x[D];
     rebuild(a);
-    int singular = 0, s = 0;
+    int s = 0;
     const int m = expm_prologue_fast<D>(G, a, x, valid, s);
     cd *out = B.E + (size_t)gidc * D * D + G.i * D;
     if (m > 5) {  // group-uniform: A (columns) to the slot, exp'd by k_expm_high
         if (valid) park<D>(G, out, a, gid, B.overflow, B.overflow_count);
         return;
     }
-    if (m == 3 || m == 5) EXPM_LOW(m, RING);
+    if (m == 3 || m == 5) expm_taylor<D, RING>(G, m, a, x, valid);
     if (valid) {  // E row-major: column i at stride D (coalesced across the group)
         cd *col = B.E + (size_t)gidc * D * D + G.i;
 #pragma unroll
         for (int j = 0; j < D; ++j) col[j * D] = x[j];
-        if (singular) atomicOr(B.status, 1);
     }
 }
 
@@ -413,7 +405,7 @@ __global__ __launch_bounds__(64, (D <= 9 ? GRAPE_EXPM_WAVES_D9 : 2)) void k_expm
     constexpr int RING = 3;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     cd *lds = reinterpret_cast<cd *>(smem_raw);
-    Group<D> G = make_group<D>(lds, threadIdx.x, EXPM_GROUP_CD(D));
+    Group<D> G = make_group<D>(lds, threadIdx.x, Geo<D>::LEAN_CD);
     const long nitems = (long)B.nb * P.Nt * P.nv;
     const long gid = (long)blockIdx.x * Geo<D>::GPW + G.g;
     const bool valid = G.lane_ok && gid < nitems;
@@ -421,19 +413,18 @@ __global__ __launch_bounds__(64, (D <= 9 ? GRAPE_EXPM_WAVES_D9 : 2)) void k_expm
     TableBuilder<D> rebuild{B.Htab + (size_t)gidc * D * D, G.i, P.dt, valid};
     cd a[D], x[D];
     rebuild(a);
-    int singular = 0, s = 0;
+    int s = 0;
     const int m = expm_prologue_fast<D>(G, a, x, valid, s);
     cd *out = B.E + (size_t)gidc * D * D + G.i * D;
     if (m > 5) {
         if (valid) park<D>(G, out, a, gid, B.overflow, B.overflow_count);
         return;
     }
-    if (m == 3 || m == 5) EXPM_LOW(m, RING);
+    if (m == 3 || m == 5) expm_taylor<D, RING>(G, m, a, x, valid);
     if (valid) {
         cd *col = B.E + (size_t)gidc * D * D + G.i;
 #pragma unroll
         for (int j = 0; j < D; ++j) col[j * D] = x[j];
-        if (singular) atomicOr(B.status, 1);
     }
 }
 
@@ -882,7 +873,7 @@ __global__ __launch_bounds__(64, (D <= 9 ? GRAPE_EXPM_GRAD_WAVES : 2)) void k_ex
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     cd *lds = reinterpret_cast<cd *>(smem_raw);
     constexpr int TILE = Geo<D>::TILE;
-    Group<D> G = make_group<D>(lds, threadIdx.x, EXPM_GROUP_CD(D));
+    Group<D> G = make_group<D>(lds, threadIdx.x, Geo<D>::LEAN_CD);
     const int nvg = P.np + (P.xadd_dep ? P.na : 0);
     const long nitems = (long)B.nb * P.Nt * nvg;
     const long gid = (long)blockIdx.x * Geo<D>::GPW + G.g;
@@ -896,14 +887,13 @@ __global__ __launch_bounds__(64, (D <= 9 ? GRAPE_EXPM_GRAD_WAVES : 2)) void k_ex
                                         P.vs[P.off_dx + u], valid, b - bx * ns);
     cd a[D], x[D];
     rebuild(a);
-    int singular = 0, s = 0;
+    int s = 0;
     const int m = expm_prologue_fast<D>(G, a, x, valid, s);
-    if (m == 3 || m == 5) EXPM_LOW(m, RING);
+    if (m == 3 || m == 5) expm_taylor<D, RING>(G, m, a, x, valid);
     if (m > 5) {
         if (valid) park<D>(G, B.ovf2_slots + (size_t)gidc * TILE + G.i * D, a, gid, B.ovf2, B.ovf2_count);
         return;  // group-uniform: the whole group parks
     }
-    if (valid && singular) atomicOr(B.status, 1);
     cd z[D], e0[D];
     grad_kernel_col<D, RING>(G, P, B, b, k, valid, z, e0);  // e0: column i of E_k
     grad_store<D>(G, P, B, b, k, u, z, x, e0, valid);

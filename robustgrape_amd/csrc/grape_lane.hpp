@@ -26,9 +26,6 @@
 
 namespace grape {
 
-#if !(defined(GRAPE_LOW_PADE) && GRAPE_LOW_PADE)
-#define GRAPE_HAVE_LANE 1
-
 // out = X . v for one column v; element j sums k = 0..D-1 in order with cmac(c, v[k], X[j][k]) --
 // the operand roles of mm_tile_r(column v, tile = X^T) in the column-form exponential.
 template <int D>
@@ -299,9 +296,5 @@ __global__ __launch_bounds__(kLaneBlock, kLaneWaves) void k_expm_chain_lane(DevP
         }
     }
 }
-
-#else
-#define GRAPE_HAVE_LANE 0
-#endif
 
 }  // namespace grape

@@ -45,27 +45,25 @@ constexpr int kLaneMaxD = 3;
 constexpr int kChainMaxD = kLaneMaxD;
 template <int D>
 bool use_chain(const DevProblem &P, const DevBatch &B) {
-    return GRAPE_HAVE_LANE && D <= kChainMaxD && B.Htab == nullptr && !(P.opts & (GRAPE_OPT_NO_LANE | GRAPE_OPT_NO_CHAIN));
+    return D <= kChainMaxD && B.Htab == nullptr && !(P.opts & (GRAPE_OPT_NO_LANE | GRAPE_OPT_NO_CHAIN));
 }
 template <int D>
 bool use_lane(const DevProblem &P, const DevBatch &B) {
-    return GRAPE_HAVE_LANE && D <= kLaneMaxD && B.Htab == nullptr && !(P.opts & GRAPE_OPT_NO_LANE);
+    return D <= kLaneMaxD && B.Htab == nullptr && !(P.opts & GRAPE_OPT_NO_LANE);
 }
 template <int D, bool ERR>
 void launch_expm_lane(const DevProblem &P, const DevBatch &B, hipStream_t st) {
-#if GRAPE_HAVE_LANE
     if constexpr (D <= kLaneMaxD) {
         const long n = (long)B.nb * P.Nt * P.nv;
         hipLaunchKernelGGL((grape::k_expm_lane<D, ERR>),
                            dim3((unsigned)((n + grape::kLaneBlock - 1) / grape::kLaneBlock)), dim3(grape::kLaneBlock), 0,
                            st, P, B);
     }
-#endif
 }
 template <int D>
 size_t expm_lds() { return (size_t)grape::Geo<D>::GPW * grape::Geo<D>::GROUP_CD * sizeof(cd); }
-template <int D>  // k_expm / k_expm_grad / k_expm_table (grape_kernels.hpp EXPM_GROUP_CD)
-size_t expm_lean_lds() { return (size_t)grape::Geo<D>::GPW * EXPM_GROUP_CD(D) * sizeof(cd); }
+template <int D>  // k_expm / k_expm_grad / k_expm_table (solve-free Taylor: no LU workspace)
+size_t expm_lean_lds() { return (size_t)grape::Geo<D>::GPW * grape::Geo<D>::LEAN_CD * sizeof(cd); }
 template <int D>
 size_t errpath_lds() {  // per group: tile + aux, then a second tile (k_err_local, k_err_grad)
     return (size_t)grape::Geo<D>::GPW * (grape::Geo<D>::GROUP_CD + grape::Geo<D>::TILE) * sizeof(cd);
@@ -284,7 +282,6 @@ hipError_t launch_sector_stage(int stage, const DevProblem &P, const DevBatch &B
     }
     if (stage == 0) {
         const long nexp = (long)B.nb * P.Nt * P.nv;
-#if GRAPE_HAVE_LANE
         if constexpr (D <= kChainMaxD) {
             if (use_chain<D>(P, B) && P.ne == 0 && P.nv == 1) {  // propagators + chunk chains per lane
                 mark(GRAPE_KERNEL_EXPM, 0);
@@ -305,7 +302,6 @@ hipError_t launch_sector_stage(int stage, const DevProblem &P, const DevBatch &B
                 return hipGetLastError();
             }
         }
-#endif
         mark(GRAPE_KERNEL_EXPM, 0);
         if (use_lane<D>(P, B))
             P.ne > 0 ? launch_expm_lane<D, true>(P, B, st) : launch_expm_lane<D, false>(P, B, st);

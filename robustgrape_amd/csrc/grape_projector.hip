@@ -899,9 +899,6 @@ __global__ __launch_bounds__(kDiagBlock) void k_sec_err_head_diag(SectorHead H, 
 // goes to LDS, and pass 1 writes row r of M_e from the block's columns; pass 2 the F_d2err_dx_add row terms.
 // Lane 0 of the group forms the target's diagonal (target_diag).  The per-element operations are
 // diag_err_blocks's; only the order of the sums over rows changed.  One C3 evaluation: 36.9 us in one lane.
-#ifndef GRAPE_ERR_HEAD_ROWS
-#define GRAPE_ERR_HEAD_ROWS 1
-#endif
 template <int S>
 __device__ void err_row(const SectorHead &H, int cl, int w, int r, size_t b, int e, int pass, const cd *u0, const cd *d,
                         cd te, cd *ue, double &t1, double &t2, cd &acc) {
@@ -1045,7 +1042,7 @@ __global__ __launch_bounds__(kDiagBlock) void k_sec_err_head_rows(SectorHead H, 
 
 hipError_t launch_sector_err_head(const SectorHead &H, int nb, hipStream_t st) {
     if (H.P.ne == 0) return hipSuccess;
-    if (H.diag && GRAPE_ERR_HEAD_ROWS && diag_group(H) <= kDiagBlock) {
+    if (H.diag && diag_group(H) <= kDiagBlock) {
         const int G = diag_group(H), EB = kDiagBlock / G, n = nb * H.P.ne;
         const size_t lds = (size_t)EB * err_rows_group_cd(H) * sizeof(cd);
         hipLaunchKernelGGL(k_sec_err_head_rows, dim3((unsigned)((n + EB - 1) / EB)), dim3(kDiagBlock), lds, st, H, nb);

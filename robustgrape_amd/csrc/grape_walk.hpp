@@ -35,7 +35,7 @@
 // element by element, before the contraction.
 //
 // Registers (D = 4): X 64 VGPRs across the walk, the A / A^2 / A^3 set 96, one vector of
-// temporaries; in k_walk_grad E lives in the lane's private LDS slot (17 complex, padded so
+// temporaries; in k_walk_grad<4> X / Y live in the lane's private LDS slot (17 complex, padded so
 // that the 16-B reads of 16 lanes hit 64 distinct banks).  The walks are compiled in their own
 // translation unit (grape_walk_inst.hip) without MachineLICM: hoisting the trig / log
 // polynomial constants of the inlined ocml calls out of the step loop pinned ~50 VGPRs and
@@ -210,21 +210,12 @@ __device__ __forceinline__ void sm_taylor_col(int nst, int i, const SM<D> &A, co
     pin<D>(x);  // the column is final here: nothing of the next one is scheduled into it
 }
 
-// column i of the high-norm regime's Taylor 30 (a2: column i of A^2, from A2 or regenerated)
-template <int D, bool KEEP_A2>
+// column i of the high-norm regime's Taylor 30 (a2: column i of A^2)
+template <int D>
 __device__ __forceinline__ void sm_taylor_col_hi(int i, const SM<D> &A, const SM<D> &A2, const SM<D> &A3, cd (&x)[D]) {
     cd a2[D];
 #pragma unroll
-    for (int j = 0; j < D; ++j) {
-        if constexpr (KEEP_A2) {
-            a2[j] = sm_el<D, true>(A2, j, i);
-        } else {
-            cd c = czero();
-#pragma unroll
-            for (int k = 0; k < D; ++k) sm_mac<D, false>(c, A, j, k, sm_el<D, false>(A, k, i));
-            a2[j] = c;
-        }
-    }
+    for (int j = 0; j < D; ++j) a2[j] = sm_el<D, true>(A2, j, i);
     constexpr int N = kWalkNstHi;
     {
         const double k0 = kWalkInvFact[3 * N], k1 = kWalkInvFact[3 * N + 1], k2 = kWalkInvFact[3 * N + 2],
@@ -252,7 +243,7 @@ __device__ __forceinline__ void sm_taylor_col_hi(int i, const SM<D> &A, const SM
 // Degree choice (grape_device.hpp expm_prologue_fast, per lane): 0 = diagonal (isdiag), 3 =
 // Taylor 6, 4 = Taylor 9, 5 = Taylor 12, 13 = Taylor 30 of A / 2^s (A scaled here) and s squarings.
 //
-// Diagonal shift (GRAPE_WALK_SHIFT): the walks exponentiate A - i mu I, i.e. they compute
+// Diagonal shift (SHIFT; WalkCfg::SHIFT): the walks exponentiate A - i mu I, i.e. they compute
 // E~ = e^{-i mu} exp(A), with mu (`choose`) the midpoint of the diagonal's imaginary parts, which
 // minimises the largest diagonal modulus -- the Rydberg 4-level sector (diagonal 0, 0, 0, B = 10)
 // drops from |A|_1 ~ 0.17 to ~ 0.09 and takes Taylor 9 (two Horner steps per column instead of
@@ -263,9 +254,6 @@ __device__ __forceinline__ void sm_taylor_col_hi(int i, const SM<D> &A, const SM
 // Taylor remainder sum_{k > m} |A|^k / k! by ~3e-17 (0.015 at m = 6, 0.1 at m = 9; 2.4e-18 at
 // 0.25, m = 12).  A diagonal A (kind 0) keeps mu = 0 when choosing, and so does an A whose shifted
 // norm still exceeds 0.25 (the high-norm regime: no Horner step to save, more FD noise).
-#ifndef GRAPE_WALK_SHIFT
-#define GRAPE_WALK_SHIFT 1
-#endif
 template <int D, bool SHIFT>
 __device__ __forceinline__ int sm_regime(SM<D> &A, int &s, double &mu, bool choose) {
     s = 0;
@@ -274,7 +262,6 @@ __device__ __forceinline__ int sm_regime(SM<D> &A, int &s, double &mu, bool choo
     for (int t = 0; t < SM<D>::NU; ++t) off = off || A.u[t].re != 0.0 || A.u[t].im != 0.0;
     if (choose) {
         mu = 0.0;
-#if GRAPE_WALK_SHIFT
         if (SHIFT && off) {
             double lo = A.d[0], hi = A.d[0];
 #pragma unroll
@@ -302,7 +289,6 @@ __device__ __forceinline__ int sm_regime(SM<D> &A, int &s, double &mu, bool choo
             }
             if (!(nsh <= 0.25)) mu = 0.0;
         }
-#endif
     }
     if (!off) return 0;  // (walk_expm shifts the diagonal itself)
     if (SHIFT) {
@@ -321,7 +307,7 @@ __device__ __forceinline__ int sm_regime(SM<D> &A, int &s, double &mu, bool choo
         nub = c == 0 ? ub : fmax(nub, ub);
     }
     if (nub <= 0.015) return 3;
-    if (GRAPE_WALK_SHIFT && SHIFT && nub <= 0.1) return 4;
+    if (SHIFT && nub <= 0.1) return 4;
     if (nub <= 0.25) return 5;
     double nA = 0.0;  // Julia's opnorm(A, 1)
 #pragma unroll
@@ -335,7 +321,7 @@ __device__ __forceinline__ int sm_regime(SM<D> &A, int &s, double &mu, bool choo
         nA = c == 0 ? cs : fmax(nA, cs);
     }
     if (nA <= 0.015) return 3;
-    if (GRAPE_WALK_SHIFT && SHIFT && nA <= 0.1) return 4;
+    if (SHIFT && nA <= 0.1) return 4;
     if (nA <= 0.25) return 5;
     if (!(nA <= 1e300)) return 5;  // NaN / Inf: propagates through the polynomial
     s = nA <= kWalkThetaHi ? 0 : (int)ceil(log2(nA / kWalkThetaHi));  // |A / 2^s|_1 <= 3.2 (Taylor 30)
@@ -347,51 +333,14 @@ __device__ __forceinline__ int sm_regime(SM<D> &A, int &s, double &mu, bool choo
     return 13;
 }
 
-// x = column i of the same polynomial without a stored A^2: column i of A^2 is A (A e_i), one
-// matrix-vector product per column (+56 FMAs at D = 4) for 32 fewer live registers.
-template <int D>
-__device__ __forceinline__ void sm_taylor_col_na2(int nst, int i, const SM<D> &A, const SM<D> &A3, cd (&x)[D]) {
-    cd a2[D];  // column i of A is read from A itself (no copy)
-#pragma unroll
-    for (int j = 0; j < D; ++j) {
-        cd c = czero();
-#pragma unroll
-        for (int k = 0; k < D; ++k) sm_mac<D, false>(c, A, j, k, sm_el<D, false>(A, k, i));
-        a2[j] = c;
-    }
-    {
-        const double k0 = ps_top(nst, 0), k1 = ps_top(nst, 1), k2 = ps_top(nst, 2), k3 = ps_top(nst, 3);
-#pragma unroll
-        for (int j = 0; j < D; ++j) {
-            x[j] = caxpy(k1, sm_el<D, false>(A, j, i), caxpy(k2, a2[j], cscale(k3, sm_el<D, false>(A3, j, i))));
-            if (j == i) x[j].re += k0;
-        }
-    }
-#pragma unroll
-    for (int st = 2; st >= 0; --st) {
-        if (st == 0 || st < nst) {  // (the last step unconditionally: no branch around it)
-            cd t[D];
-            sm_matvec<D, false>(A3, x, t);
-            const double k0 = inv_fact(3 * st), k1 = inv_fact(3 * st + 1), k2 = inv_fact(3 * st + 2);
-#pragma unroll
-            for (int j = 0; j < D; ++j) {
-                x[j] = caxpy(k1, sm_el<D, false>(A, j, i), caxpy(k2, a2[j], t[j]));
-                if (j == i) x[j].re += k0;
-            }
-        }
-    }
-    pin<D>(x);
-}
-
 // exp(A), column by column into sink(i, column i).  The squaring path (kind 13, rare) parks
 // the scaled approximant in the lane's global scratch slot `scr` (two D x D column-major
 // tiles) and squares it there element by element, so that it adds no live registers to the
 // common path.  FENCE: pin every column and keep the scheduler from overlapping them (register
-// discipline at D = 4; at D <= 3 the columns and sectors may interleave for ILP).  KEEP_A2:
-// keep A^2 through the column loop (else regenerate its columns, sm_taylor_col_na2).
+// discipline at D = 4; at D <= 3 the columns and sectors may interleave for ILP).
 // mu: the diagonal shift (sm_regime): chosen here and returned (choose), or the nominal's (an
 // eps-variant); the columns are those of E~ = exp(A - i mu I).
-template <int D, bool FENCE, bool KEEP_A2, bool SHIFT, class Sink>
+template <int D, bool FENCE, bool SHIFT, class Sink>
 __device__ __forceinline__ void walk_expm(SM<D> &A, cd *scr, double &mu, bool choose, Sink &&sink) {
     int s = 0;
     const int kind = sm_regime<D, SHIFT>(A, s, mu, choose);
@@ -410,16 +359,12 @@ __device__ __forceinline__ void walk_expm(SM<D> &A, cd *scr, double &mu, bool ch
     }
     SM<D> A2, A3;
     sm_cube<D>(A, A2, A3);
-    auto col = [&](int nst, int i, cd (&x)[D]) {
-        if constexpr (KEEP_A2) sm_taylor_col<D>(nst, i, A, A2, A3, x);
-        else sm_taylor_col_na2<D>(nst, i, A, A3, x);
-    };
     if (kind != 13) {
         const int nst = kind == 3 ? 1 : kind == 4 ? 2 : 3;
 #pragma unroll
         for (int i = 0; i < D; ++i) {
             cd x[D];
-            col(nst, i, x);
+            sm_taylor_col<D>(nst, i, A, A2, A3, x);
             sink(i, x);
             if (FENCE) __builtin_amdgcn_sched_barrier(0);
         }
@@ -429,7 +374,7 @@ __device__ __forceinline__ void walk_expm(SM<D> &A, cd *scr, double &mu, bool ch
 #pragma unroll
     for (int i = 0; i < D; ++i) {  // (unrolled: register arrays are only ever indexed by constants)
         cd x[D];
-        sm_taylor_col_hi<D, KEEP_A2>(i, A, A2, A3, x);
+        sm_taylor_col_hi<D>(i, A, A2, A3, x);
 #pragma unroll
         for (int j = 0; j < D; ++j) T[i * D + j] = x[j];
     }
@@ -508,10 +453,10 @@ struct X2 {
 // Unconditional loads (the second one clamped into the vector): a load under a branch leaves the
 // compiler without a static count of the outstanding vector-memory operations, and it then waits
 // with vmcnt(0) -- for every store of the step too -- before the prefetched value is used.
-// xs: the transposed controls (B.xT) at this lane's evaluation, consecutive values `stride` apart
-__device__ __forceinline__ X2 walk_load_x(int n, const double *xs, int stride) {  // n (uniform) <= 2 values
+// xs: consecutive values of this lane's row of x
+__device__ __forceinline__ X2 walk_load_x(int n, const double *xs) {  // n (uniform) <= 2 values
     X2 r;
-    const double a = xs[0], b = xs[n > 1 ? stride : 0];
+    const double a = xs[0], b = xs[n > 1 ? 1 : 0];
     r.v0 = n > 0 ? a : 0.0;
     r.v1 = n > 1 ? b : 0.0;
     return r;
@@ -634,13 +579,12 @@ struct MStore<D, true> {
 };
 
 // Launch geometry: one lane per (chunk c, evaluation be) -- the evaluation fastest, so that a
-// wave's per-step reads of the transposed controls (B.xT) and stores of its F_dx terms (B.sec_part,
-// evaluation-fastest) are contiguous -- and group of NS sectors (w0 = NS * blockIdx.y);
+// wave's stores of its F_dx terms (B.sec_part, evaluation-fastest) are contiguous -- and group of NS sectors (w0 = NS * blockIdx.y);
 // sub-evaluation of sector w: be * nsec + w.  Lanes past the end (ok = false) run the walk on
 // clamped indices and store nothing, so that every loop in the walks has a wave-uniform trip
 // count (scalar loads of the term tables).
 struct WalkLane {
-    int w0, be, c, nbe;  // nbe: evaluations of the launch (the stride of B.xT and B.sec_part)
+    int w0, be, c, nbe;  // nbe: evaluations of the launch (the stride of B.sec_part)
     long slot;           // the lane's scratch slot (NS consecutive pairs of D x D tiles)
     bool ok;
 };
@@ -668,113 +612,92 @@ __device__ __forceinline__ WalkLane walk_lane(const DevProblem &P, const DevBatc
     return L;
 }
 
-#ifndef GRAPE_WALK_G4_KEEP_A2_GRAD  // k_walk_grad<4>: keep A'^2 of the eps-variant (0: regenerate its columns)
-#define GRAPE_WALK_G4_KEEP_A2_GRAD 1
-#endif
-#ifndef GRAPE_WALK_IMG4_KEEP_A2  // k_walk_img<4>: keep each variant's A^2 (0: regenerate its columns)
-#define GRAPE_WALK_IMG4_KEEP_A2 1
-#endif
-#ifndef GRAPE_WALK_F4_WAVES  // k_walk_fwd<4>: waves per SIMD
+// The build's knobs of the walks: plain numbers (waves per SIMD for __launch_bounds__), A/B'd from one tree
+// with -D (scripts/build_variants.py), and the three code paths bench.py's FLOP model reads from the build's
+// defines.  What was measured with them is in DESIGN.md 9 and 10.
+#ifndef GRAPE_WALK_F4_WAVES  // k_walk_fwd<4>
 #define GRAPE_WALK_F4_WAVES 2
 #endif
-#ifndef GRAPE_WALK_F4_FENCE  // k_walk_fwd<4>: fence the exponential's columns
-#define GRAPE_WALK_F4_FENCE 1
+#ifndef GRAPE_WALK_F3_WAVES  // k_walk_fwd<3>
+#define GRAPE_WALK_F3_WAVES 2
 #endif
-#ifndef GRAPE_WALK_G4_KEEP_A2_NOM
-#define GRAPE_WALK_G4_KEEP_A2_NOM 1
+#ifndef GRAPE_WALK_F22_WAVES  // k_walk_fwd<2, 2>
+#define GRAPE_WALK_F22_WAVES 3
 #endif
-#ifndef GRAPE_WALK_G4_WAVES
+#ifndef GRAPE_WALK_G4_WAVES  // k_walk_grad<4> (recomputed propagators)
 #define GRAPE_WALK_G4_WAVES 1
 #endif
 #ifndef GRAPE_WALK_G4S_WAVES  // k_walk_grad<4> with stored propagators
 #define GRAPE_WALK_G4S_WAVES 1
 #endif
-#ifndef GRAPE_WALK_G4_XLDS  // k_walk_grad<4>: 1 = X / Y in the LDS slot and E in registers, 0 = the reverse
-#define GRAPE_WALK_G4_XLDS 1
-#endif
-#ifndef GRAPE_WALK_I21_WAVES  // k_walk_img occupancy: one 2-level sector per lane ...
-#define GRAPE_WALK_I21_WAVES 3
-#endif
-#ifndef GRAPE_WALK_I22_WAVES  // ... or two
-#define GRAPE_WALK_I22_WAVES 2
-#endif
-#ifndef GRAPE_WALK_IMG2_NS1  // the 2-level image walks (error sources) with one sector per lane
-#define GRAPE_WALK_IMG2_NS1 0
-#endif
-#ifndef GRAPE_WALK_FDX_IN_ERR  // F_dx traces in k_walk_err_grad (k_walk_img_sum: W chunk sums only)
-#define GRAPE_WALK_FDX_IN_ERR 1
-#endif
-// ... and those sums in the 2-level image walk itself (LDS accumulators; needs GRAPE_WALK_IMG2_NS1).
-// Off: measured slower, C3 580 k -> 569-570 k evals/s (k_walk_img +1.55 ms, k_walk_img_sum -1.0 ms
-// per bench step, A/B in one GPU call)
-#ifndef GRAPE_WALK_IMG_WSUM
-#define GRAPE_WALK_IMG_WSUM 0
-#endif
-constexpr int kWsumMaxE = 4;
-// k_walk_grad with several sectors per lane (the 2-level classes without error sources) writes ONE
-// F_dx part per lane row -- its sectors' terms summed in sector order -- so k_sec_reduce reads
-// nsec / NS parts for that class (grape_walk_api.hpp walk_parts)
-#ifndef GRAPE_WALK_PRESUM
-#define GRAPE_WALK_PRESUM 1
-#endif
-constexpr bool kWalkPresum = GRAPE_WALK_PRESUM;
-  // error sources whose W chunk sums the 2-level image walk accumulates
-#ifndef GRAPE_WALK_IMG_LDS
-#define GRAPE_WALK_IMG_LDS 1
-#endif
-#ifndef GRAPE_WALK_SHIFT_MIN_D  // the diagonal shift for classes of >= this many levels
-#define GRAPE_WALK_SHIFT_MIN_D 3
-#endif
-#ifndef GRAPE_WALK_F3_WAVES  // k_walk_fwd<3>: waves per SIMD
-#define GRAPE_WALK_F3_WAVES 2
-#endif
 #ifndef GRAPE_WALK_G3_WAVES  // k_walk_grad<3, 1> (recomputed propagators)
 #define GRAPE_WALK_G3_WAVES 2
-#endif
-#ifndef GRAPE_WALK_F22_WAVES  // k_walk_fwd<2, 2>: waves per SIMD
-#define GRAPE_WALK_F22_WAVES 3
-#endif
-#ifndef GRAPE_WALK_G22_WAVES  // k_walk_grad<2, 2>
-#define GRAPE_WALK_G22_WAVES 3
 #endif
 #ifndef GRAPE_WALK_G3S_WAVES  // k_walk_grad<3, 1> with stored propagators
 #define GRAPE_WALK_G3S_WAVES 1
 #endif
-#ifndef GRAPE_WALK_GAUGE2_WAVES
+#ifndef GRAPE_WALK_G22_WAVES  // k_walk_grad<2, 2>
+#define GRAPE_WALK_G22_WAVES 3
+#endif
+#ifndef GRAPE_WALK_I21_WAVES  // k_walk_img<2, 1>
+#define GRAPE_WALK_I21_WAVES 3
+#endif
+#ifndef GRAPE_WALK_I22_WAVES  // k_walk_img<2, 2>
+#define GRAPE_WALK_I22_WAVES 2
+#endif
+#ifndef GRAPE_WALK_GAUGE2_WAVES  // phase-covariant chunk walks of 2 levels ...
 #define GRAPE_WALK_GAUGE2_WAVES 4
 #endif
-#ifndef GRAPE_WALK_GAUGE3_WAVES
+#ifndef GRAPE_WALK_GAUGE3_WAVES  // ... of 3 ...
 #define GRAPE_WALK_GAUGE3_WAVES 3
 #endif
-#ifndef GRAPE_WALK_GAUGE4_WAVES
+#ifndef GRAPE_WALK_GAUGE4_WAVES  // ... and of 4
 #define GRAPE_WALK_GAUGE4_WAVES 2
+#endif
+#ifndef GRAPE_WALK_FWD_M_WAVES  // the merged forward walk (120 VGPRs with E~ in SGPRs)
+#define GRAPE_WALK_FWD_M_WAVES 4
+#endif
+#ifndef GRAPE_WALK_MERGED_WAVES  // the merged matrix gradient walk (222 VGPRs with E~ in registers)
+#define GRAPE_WALK_MERGED_WAVES 2
+#endif
+#ifndef GRAPE_WALK_R1_WAVES  // the merged rank-one gradient walk (108 VGPRs with E~ in SGPRs)
+#define GRAPE_WALK_R1_WAVES 3
+#endif
+#ifndef GRAPE_WALK_WIDE_FWD_WAVES  // the wide forward walk (10 VGPRs of state)
+#define GRAPE_WALK_WIDE_FWD_WAVES 4
+#endif
+#ifndef GRAPE_WALK_WIDE_GRAD_WAVES  // the wide gradient walk
+#define GRAPE_WALK_WIDE_GRAD_WAVES 4
+#endif
+#ifndef GRAPE_WALK_WSUM_LAB_WAVES  // k_walk_wsum_lab
+#define GRAPE_WALK_WSUM_LAB_WAVES 2
+#endif
+#ifndef GRAPE_WALK_ERR_LAB_WAVES  // k_walk_err_lab at 2 and 3 levels
+#define GRAPE_WALK_ERR_LAB_WAVES 2
+#endif
+#ifndef GRAPE_WALK_ERR_LAB4_WAVES  // k_walk_err_lab<4>: four 4 x 4 complex matrices live (256 VGPRs) at the peak
+#define GRAPE_WALK_ERR_LAB4_WAVES 2
+#endif
+#ifndef GRAPE_WALK_TWIN_SUM  // merged gradient walk, twin class B: one summed state for both sectors
+#define GRAPE_WALK_TWIN_SUM 1
+#endif
+#ifndef GRAPE_WALK_LADDER_CONTR  // ladder classes: the contraction grouped by charge difference
+#define GRAPE_WALK_LADDER_CONTR 1
 #endif
 template <int D, int NS>
 struct WalkCfg {
     static constexpr bool FENCE = D >= 4;        // per-column scheduling fences (register discipline)
-    static constexpr bool E_LDS_FWD = false;     // k_walk_fwd keeps E in registers
-    static constexpr bool X_LDS = D >= 4 && NS == 1 && GRAPE_WALK_G4_XLDS;  // k_walk_grad: X / Y in LDS
-    static constexpr bool E_LDS_GRAD = D >= 4 && NS == 1 && !GRAPE_WALK_G4_XLDS;  // ... or E in LDS
-    // k_walk_grad<4> keeps A'^2 too (round 3: 2.28-2.32 -> 2.20 ms per C2 pass; the stored-propagator
-    // kernel has the registers at one wave per SIMD); the image walk regenerates its columns
-    static constexpr bool KEEP_A2_GRAD = D < 4 || GRAPE_WALK_G4_KEEP_A2_GRAD;
-    static constexpr bool KEEP_A2_IMG = D < 4 || GRAPE_WALK_IMG4_KEEP_A2;
-    static constexpr bool KEEP_A2_NOM = D < 4 || GRAPE_WALK_G4_KEEP_A2_NOM;
+    static constexpr bool X_LDS = D >= 4 && NS == 1;  // k_walk_grad: X / Y in the lane's LDS slot, E in registers
     static constexpr int WAVES_FWD = D <= 2 ? (NS == 1 ? 4 : NS == 2 ? GRAPE_WALK_F22_WAVES : 3)
                                    : D == 3 ? GRAPE_WALK_F3_WAVES : GRAPE_WALK_F4_WAVES;
-    static constexpr bool FENCE_FWD = D >= 4 && GRAPE_WALK_F4_FENCE;
     static constexpr int WAVES_GRAD = D <= 2 ? (NS == 1 ? 4 : NS == 2 ? GRAPE_WALK_G22_WAVES : 2)
                                     : D == 3 ? (NS == 1 ? GRAPE_WALK_G3_WAVES : 1) : GRAPE_WALK_G4_WAVES;
     static constexpr int WAVES_GRAD_STORED = D <= 2 ? (NS == 1 ? 3 : 2) : D == 3 ? GRAPE_WALK_G3S_WAVES : GRAPE_WALK_G4S_WAVES;
     static constexpr int WAVES_IMG = D <= 2 ? (NS == 1 ? GRAPE_WALK_I21_WAVES : GRAPE_WALK_I22_WAVES) : 1;  // k_walk_img
-    static constexpr bool IMG_LDS = D >= 4 && GRAPE_WALK_IMG_LDS;      // k_walk_img: eps2 propagators in LDS
-    // k_walk_img sums W_e over the chunk in LDS (kWalkBlock x kWsumMaxE x D^2 entries: 64 KB at D = 2)
-    // and k_walk_img_sum is not launched (ne <= kWsumMaxE)
-    static constexpr bool IMG_WSUM = D == 2 && NS == 1 && GRAPE_WALK_IMG_WSUM && GRAPE_WALK_FDX_IN_ERR;
-    // the diagonal shift + Taylor 9 (sm_regime) for the 4-level class only: it pays where the
-    // Taylor-12 columns dominate; the smaller classes (Taylor 6 at C2) measured slower with its
-    // bookkeeping (k_walk_fwd<2,2> 0.295 -> 0.34 ms per pass) and keep the unshifted walk bitwise
-    static constexpr bool SHIFT = D >= GRAPE_WALK_SHIFT_MIN_D;
+    static constexpr bool IMG_LDS = D >= 4;      // k_walk_img: eps2 propagators in LDS
+    // the diagonal shift + Taylor 9 (sm_regime) where the Taylor-12 columns dominate; the 2-level classes
+    // (Taylor 6 at C2) keep the unshifted walk bitwise
+    static constexpr bool SHIFT = D >= 3;
     // phase-covariant classes (GAUGE): E~, E and the walk state only -- no exponential per step
     static constexpr int WAVES_GAUGE = D <= 2 ? (NS >= 3 ? 2 : GRAPE_WALK_GAUGE2_WAVES)
                                               : D == 3 ? GRAPE_WALK_GAUGE3_WAVES : GRAPE_WALK_GAUGE4_WAVES;
@@ -820,7 +743,7 @@ constexpr int kEwStride = D * D + 1;
 // phi = a ((x_k + eps) - x_k).  So a lane computes ONE exponential (E~, at its start) instead of
 // one per step and variant; per step it forms E_k from E~ and the D phases of its levels, and
 //   (E'_k - E_k)_rj = E_rj (rho_r + conj(rho_j) + rho_r conj(rho_j)),   1 + rho_j = e^{i phi N_j},
-// with rho computed without cancellation (gauge_rho), so the reference's forward difference
+// with f_rj computed without cancellation (gauge_fd_weights_dn), so the reference's forward difference
 // (UnitaryCalculations.jl:48-56) is formed from the exact perturbed propagator: same quantity, less
 // rounding noise than two separate exponentials.  The charges are wave-uniform (one sector per
 // workgroup row: scalar loads), so the per-level powers below are scalar-uniform loops.
@@ -852,9 +775,6 @@ __device__ __forceinline__ cd gauge_pow(cd z, int n) {
 // p = e^{i t}: the per-step phase base of the phase-covariant walks (grape_cis.hpp: Cody-Waite reduction
 // and fdlibm kernels, <= 0.67 ulp; the library sincos above |t| = 1e5).  Every gauge kernel (forward,
 // gradient, image walk, eval1) takes its phases here, so the walks of one evaluation agree bit for bit.
-#ifndef GRAPE_GAUGE_FAST_CIS  // 0: the library sincos (A/B)
-#define GRAPE_GAUGE_FAST_CIS 1
-#endif
 // the constants of grape_cis::cis_fast as opaque SGPR pairs: an empty asm hides the literal from the
 // instruction selector, so each Horner step is one v_fma_f64 with a scalar operand (not a v_fmac_f64 on
 // a VGPR copy of the literal, two v_mov_b32 per constant and step: the walks are built without
@@ -868,12 +788,8 @@ struct CisConst {
 };
 __device__ __forceinline__ cd gauge_cis(double t) {
     double s, c;
-#if GRAPE_GAUGE_FAST_CIS
     if (fabs(t) <= grape_cis::kCisFast) grape_cis::cis_fast(t, s, c, CisConst());
     else sincos(t, &s, &c);
-#else
-    sincos(t, &s, &c);
-#endif
     return cmake(c, s);
 }
 // e^{i phi} - 1 without cancellation: (-2 sin^2(phi / 2), sin phi); Taylor for the FD-sized
@@ -892,33 +808,9 @@ __device__ __forceinline__ cd cis_m1(double phi) {
     const double sh = sin(0.5 * phi);
     return cmake(-2.0 * sh * sh, sin(phi));
 }
-// rho = (1 + q)^n - 1 by rho <- rho + q + q rho (no cancellation), n wave-uniform
-__device__ __forceinline__ cd gauge_rho(cd q, int n) {
-    cd r = czero();
-#pragma unroll 1
-    for (int m = 0; m < n; ++m) r = cadd(cadd(r, q), cmul(q, r));
-    return r;
-}
-// the difference weights f_rj = (1 + rho_r)(1 + conj(rho_j)) - 1 = rho_r + conj(rho_j) + rho_r conj(rho_j)
-// (no cancellation) of (E' - E)_rj = E_rj f_rj, formed once per pair r < j: f_jr = conj(f_rj) bit for bit
-// (the same roundings, conjugated)
-template <int D>
-__device__ __forceinline__ void gauge_fd_weights(const cd (&rho)[D], cd (&f)[kGaugePairs<D>]) {
-#pragma unroll
-    for (int r = 0; r < D; ++r) {
-#pragma unroll
-        for (int j = r + 1; j < D; ++j) {
-            const cd rj = cconj(rho[j]);
-            f[gauge_pair(D, r, j)] = cadd(cadd(rho[r], rj), cmul(rho[r], rj));
-        }
-    }
-}
-// GRAPE_GAUGE_FD_DN (default): the weights straight from the charge differences, f_rj = e^{i phi (N_r - N_j)} - 1 =
-// rho(N_r - N_j) (conjugated for N_r < N_j; rho(1) = q exactly), no per-level rho -- the same quantity,
-// other roundings (<= a few ulp of f)
-#ifndef GRAPE_GAUGE_FD_DN  // (default: C2 43.7-44.0 -> 45.3-45.4 M evals/s, A/B in one GPU call)
-#define GRAPE_GAUGE_FD_DN 1
-#endif
+// the difference weights of (E' - E)_rj = E_rj f_rj, formed once per pair r < j (f_jr = conj(f_rj) bit for bit),
+// straight from the charge differences: f_rj = e^{i phi (N_r - N_j)} - 1 = rho(N_r - N_j) with
+// rho(m) = (1 + q)^m - 1 by rho <- rho + q + q rho (no cancellation; rho(1) = q exactly), conjugated for N_r < N_j
 template <int D>
 __device__ __forceinline__ void gauge_fd_weights_dn(cd q, const GaugeN<D> &g, cd (&f)[kGaugePairs<D>]) {
 #pragma unroll
@@ -957,7 +849,7 @@ __device__ __forceinline__ void gauge_base(const DevProblem &P, cptr<cd> ops, cd
         SM<D> A[1];
         walk_build<D, 1>(P, ops + (size_t)w * P.sec_ops, X0, 1, none, A);
         double mu0 = 0.0;
-        walk_expm<D, false, true, false>(A[0], scr, mu0, true, [&](int i, const cd (&x)[D]) {
+        walk_expm<D, false, false>(A[0], scr, mu0, true, [&](int i, const cd (&x)[D]) {
 #pragma unroll
             for (int j = 0; j < D; ++j) gE[(w * D + j) * D + i] = x[j];
         });
@@ -988,7 +880,7 @@ __device__ __forceinline__ const cd *gauge_base_lds(const DevProblem &P, cptr<cd
         SM<D> A[1];
         walk_build<D, 1>(P, ops + (size_t)w * P.sec_ops, X0, 1, none, A);
         double mu0 = 0.0;
-        walk_expm<D, false, true, false>(A[0], scr, mu0, true, [&](int i, const cd (&x)[D]) {
+        walk_expm<D, false, false>(A[0], scr, mu0, true, [&](int i, const cd (&x)[D]) {
 #pragma unroll
             for (int j = 0; j < D; ++j) gE[(w * D + j) * D + i] = x[j];
         });
@@ -1068,8 +960,7 @@ __device__ __forceinline__ void walk_fwd_body(const DevProblem &P, const DevBatc
     constexpr int TS = D * D;
     const WalkLane L = walk_lane<NS>(P, B, vb);
     const int ns = P.nsec > 1 ? P.nsec : 1;
-    const double *xt = B.xT + (size_t)L.be * (kWalkXRow ? P.nx : 1);  // x[q] of this evaluation at xt[q * xs]
-    const int xs = kWalkXRow ? 1 : L.nbe;
+    const double *xt = B.xT + (size_t)L.be * P.nx;  // this evaluation's row of x (B.xT = B.x)
     const cptr<cd> ops = as_constant(P.ops) + (size_t)L.w0 * P.sec_ops;
     cd *scr = B.wscr + (size_t)L.slot * NS * 2 * TS;
     Pert none;
@@ -1077,15 +968,11 @@ __device__ __forceinline__ void walk_fwd_body(const DevProblem &P, const DevBatc
     none.index = 0;
     none.delta = 0.0;
     const size_t lanes = (size_t)vb.gx * kWalkBlock, lane = (size_t)vb.x * kWalkBlock + threadIdx.x;
-    MStore<D, C::E_LDS_FWD> E;
-    if constexpr (C::E_LDS_FWD) {
-        __shared__ cd lds[kWalkBlock * MStore<D, true>::kStride];
-        E.p = MStore<D, true>::slot(lds);
-    }
+    MStore<D, false> E;
     WalkX X;
-    walk_set_xa(X, walk_load_x(P.na, xt + (size_t)P.np * P.Nt * xs, xs));  // x_add
+    walk_set_xa(X, walk_load_x(P.na, xt + (size_t)P.np * P.Nt));  // x_add
     const int k0 = L.c * P.L;
-    X2 xn = walk_load_x(P.np, xt + (size_t)min(k0, P.Nt - 1) * P.np * xs, xs);
+    X2 xn = walk_load_x(P.np, xt + (size_t)min(k0, P.Nt - 1) * P.np);
     cd Q[NE][D][D];
     WalkPhase ph[NE];
 #pragma unroll
@@ -1109,7 +996,7 @@ __device__ __forceinline__ void walk_fwd_body(const DevProblem &P, const DevBatc
         const int k = min(k0 + jj, P.Nt - 1);
         const bool act = k0 + jj < P.Nt;
         walk_set_xk(X, xn);
-        xn = walk_load_x(P.np, xt + (size_t)min(k + 1, P.Nt - 1) * P.np * xs, xs);  // next step's controls
+        xn = walk_load_x(P.np, xt + (size_t)min(k + 1, P.Nt - 1) * P.np);  // next step's controls
         SM<D> A[GAUGE ? 1 : NE];
         cd p1 = czero();
         if constexpr (GAUGE) {
@@ -1125,7 +1012,7 @@ __device__ __forceinline__ void walk_fwd_body(const DevProblem &P, const DevBatc
                 gauge_phases<D>(p1, gn[w], dph);
                 gauge_prop<D>(Et[w], dph, E);
             } else {
-                walk_expm<D, C::FENCE_FWD, true, C::SHIFT>(A[w], scr + (size_t)w * 2 * TS, mu, true, [&](int i, const cd (&x)[D]) {
+                walk_expm<D, C::FENCE, C::SHIFT>(A[w], scr + (size_t)w * 2 * TS, mu, true, [&](int i, const cd (&x)[D]) {
 #pragma unroll
                     for (int j = 0; j < D; ++j) E.set(j, i, x[j]);
                 });
@@ -1191,6 +1078,9 @@ void k_walk_fwd(DevProblem P, DevBatch B) {
 // X, Y and contractions stay per sector: M differs between them in general)
 // GAUGE: a phase-covariant class (P.gauge; NVG == 1): E_k from E~ and the level phases, and the
 // eps-variant's difference E' - E = E o f with f_rj = rho_r + conj(rho_j) + rho_r conj(rho_j)
+// Several sectors per lane (NS > 1: the 2-level classes without error sources) write ONE F_dx part per lane
+// row -- the sectors' terms summed in sector order -- so k_sec_reduce reads nsec / NS parts for that class
+// (grape_walk_api.hpp grad_parts)
 template <int D, int NS, bool STORED, int NVG, bool TWIN = false, bool GAUGE = false>
 __device__ __forceinline__ void walk_grad_body(const DevProblem &P, const DevBatch &B, const VBlock vb) {
     using C = WalkCfg<D, NS>;
@@ -1201,8 +1091,7 @@ __device__ __forceinline__ void walk_grad_body(const DevProblem &P, const DevBat
     constexpr int TS = D * D;
     const WalkLane L = walk_lane<NS>(P, B, vb);
     const int ns = P.nsec > 1 ? P.nsec : 1;
-    const double *xt = B.xT + (size_t)L.be * (kWalkXRow ? P.nx : 1);  // x[q] of this evaluation at xt[q * xs]
-    const int xs = kWalkXRow ? 1 : L.nbe;
+    const double *xt = B.xT + (size_t)L.be * P.nx;  // this evaluation's row of x (B.xT = B.x)
     const cptr<cd> ops = as_constant(P.ops) + (size_t)L.w0 * P.sec_ops;
     cd *scr = B.wscr + (size_t)L.slot * NS * 2 * TS;
     Pert none;
@@ -1210,14 +1099,13 @@ __device__ __forceinline__ void walk_grad_body(const DevProblem &P, const DevBat
     none.index = 0;
     none.delta = 0.0;
     // X_{k-1} = C_{k-1} M C_{k-1}^dag of every sector (M'_c at the chunk start); Y_k in place
-    constexpr bool XL = C::X_LDS && !STORED, EL = C::E_LDS_GRAD && !STORED;
+    constexpr bool XL = C::X_LDS && !STORED;
     MStore<D, XL> X[NS];
-    MStore<D, EL> E[NE];
-    if constexpr (XL || EL) {
-        static_assert(NS == 1 && !(XL && EL), "one LDS slot per lane");
+    MStore<D, false> E[NE];
+    if constexpr (XL) {
+        static_assert(NS == 1, "one LDS slot per lane");
         __shared__ cd lds[kWalkBlock * MStore<D, true>::kStride];
-        if constexpr (XL) X[0].p = MStore<D, true>::slot(lds);
-        else E[0].p = MStore<D, true>::slot(lds);
+        X[0].p = MStore<D, true>::slot(lds);
     }
     const size_t lanes = (size_t)vb.gx * kWalkBlock, lane = (size_t)vb.x * kWalkBlock + threadIdx.x;
     auto ew = [&](int jj, int w) { return B.Ew + ((((size_t)vb.y * P.L + jj) * NS + w) * kEwStride<D>) * lanes + lane; };
@@ -1261,13 +1149,13 @@ __device__ __forceinline__ void walk_grad_body(const DevProblem &P, const DevBat
         }
     }
     WalkX XV;
-    walk_set_xa(XV, walk_load_x(P.na, xt + (size_t)P.np * P.Nt * xs, xs));
+    walk_set_xa(XV, walk_load_x(P.na, xt + (size_t)P.np * P.Nt));
     const int k0 = L.c * P.L;
-    X2 xn = walk_load_x(P.np, xt + (size_t)min(k0, P.Nt - 1) * P.np * xs, xs);
+    X2 xn = walk_load_x(P.np, xt + (size_t)min(k0, P.Nt - 1) * P.np);
     const cptr<VSpec> vs = as_constant(P.vs);
     cd Et[GAUGE ? NE : 1][D][D];  // GAUGE: E~ of the lane's sectors (the forward walk's bits)
     GaugeN<D> gn[GAUGE ? NE : 1];
-    cd fwp[GAUGE ? NE : 1][kGaugePairs<D>];  // GAUGE: this step's difference weights (gauge_fd_weights)
+    cd fwp[GAUGE ? NE : 1][kGaugePairs<D>];  // GAUGE: this step's difference weights (gauge_fd_weights_dn)
     if constexpr (GAUGE) {
         gauge_base<D, NE>(P, ops, scr, Et);
 #pragma unroll
@@ -1278,7 +1166,7 @@ __device__ __forceinline__ void walk_grad_body(const DevProblem &P, const DevBat
         const int k = min(k0 + jj, P.Nt - 1);
         const bool act = L.ok && k0 + jj < P.Nt;
         walk_set_xk(XV, xn);
-        xn = walk_load_x(P.np, xt + (size_t)min(k + 1, P.Nt - 1) * P.np * xs, xs);  // next step's controls
+        xn = walk_load_x(P.np, xt + (size_t)min(k + 1, P.Nt - 1) * P.np);  // next step's controls
         if constexpr (GAUGE) {
             const double xk = XV.k0, xe = xk + P.eps;  // the reference's perturbed control (Pert delta = eps)
             const cd p1 = gauge_cis(P.gauge_a * xk), q = cis_m1(P.gauge_a * (xe - xk));  // (xe - xk: exact)
@@ -1288,14 +1176,7 @@ __device__ __forceinline__ void walk_grad_body(const DevProblem &P, const DevBat
                 gauge_phases<D>(p1, gn[w], dph);
                 gauge_prop<D>(Et[w], dph, E[w]);
                 mu[w] = 0.0;
-#if GRAPE_GAUGE_FD_DN
                 gauge_fd_weights_dn<D>(q, gn[w], fwp[w]);
-#else
-                cd rho[D];  // e^{i phi N_j} - 1
-#pragma unroll
-                for (int j = 0; j < D; ++j) rho[j] = gauge_rho(q, gn[w].n[j]);
-                gauge_fd_weights<D>(rho, fwp[w]);
-#endif
             }
         } else if constexpr (STORED) {  // this step's propagators; the next step's loads go out now
 #pragma unroll
@@ -1323,7 +1204,7 @@ __device__ __forceinline__ void walk_grad_body(const DevProblem &P, const DevBat
             walk_build<D, NE>(P, ops, XV, k + 1, none, A);
 #pragma unroll
             for (int w = 0; w < NE; ++w)
-                walk_expm<D, C::FENCE, C::KEEP_A2_NOM, C::SHIFT>(A[w], scr + (size_t)w * 2 * TS, mu[w], true, [&](int i, const cd (&x)[D]) {
+                walk_expm<D, C::FENCE, C::SHIFT>(A[w], scr + (size_t)w * 2 * TS, mu[w], true, [&](int i, const cd (&x)[D]) {
 #pragma unroll
                     for (int j = 0; j < D; ++j) E[w].set(j, i, x[j]);
                 });
@@ -1374,7 +1255,7 @@ __device__ __forceinline__ void walk_grad_body(const DevProblem &P, const DevBat
 #pragma unroll
                 for (int t = 0; t < NSH; ++t) {
                     const int w = we * NSH + t;
-                    if constexpr (kWalkPresum && NS > 1) {
+                    if constexpr (NS > 1) {
                         tot += s[t];
                     } else {
                         double *dst = act ? B.sec_part + ((((size_t)(L.w0 + w) * P.Nt) + k) * P.nvg) * L.nbe + L.be
@@ -1383,7 +1264,7 @@ __device__ __forceinline__ void walk_grad_body(const DevProblem &P, const DevBat
                     }
                 }
             }
-            if constexpr (kWalkPresum && NS > 1) {
+            if constexpr (NS > 1) {
                 double *dst = act ? B.sec_part + ((((size_t)(L.w0 / NS) * P.Nt) + k) * P.nvg) * L.nbe + L.be
                                   : reinterpret_cast<double *>(B.sink);
                 *dst = tot;
@@ -1394,13 +1275,13 @@ __device__ __forceinline__ void walk_grad_body(const DevProblem &P, const DevBat
         for (int u = 0; u < (GAUGE ? 0 : NVG > 0 ? NVG : P.nvg); ++u) {
             SM<D> Ap[NE];
             walk_build<D, NE>(P, ops, XV, k + 1, pload(vs, P.off_dx + u), Ap);
-            double tot = 0.0;  // (kWalkPresum: the lane's sectors summed, in sector order)
+            double tot = 0.0;  // (NS > 1: the lane's sectors summed, in sector order)
 #pragma unroll
             for (int we = 0; we < NE; ++we) {
                 double s[NSH];
 #pragma unroll
                 for (int t = 0; t < NSH; ++t) s[t] = 0.0;
-                walk_expm<D, C::FENCE, C::KEEP_A2_GRAD, C::SHIFT>(Ap[we], scr + (size_t)we * 2 * TS, mu[we], false, [&](int j, const cd (&x)[D]) {
+                walk_expm<D, C::FENCE, C::SHIFT>(Ap[we], scr + (size_t)we * 2 * TS, mu[we], false, [&](int j, const cd (&x)[D]) {
                     if constexpr (NSH == 1) {
                         const auto &Yj = X[we].opaque();  // row j of Y and column j of E read here, after
                         const auto &Ej = E[we].opaque();  // column j of E'
@@ -1431,7 +1312,7 @@ __device__ __forceinline__ void walk_grad_body(const DevProblem &P, const DevBat
 #pragma unroll
                 for (int t = 0; t < NSH; ++t) {
                     const int w = we * NSH + t;
-                    if constexpr (kWalkPresum && NS > 1) {
+                    if constexpr (NS > 1) {
                         tot += s[t];
                     } else {
                         // unconditional store (inactive lanes write the sink): exact vmcnt accounting
@@ -1441,7 +1322,7 @@ __device__ __forceinline__ void walk_grad_body(const DevProblem &P, const DevBat
                     }
                 }
             }
-            if constexpr (kWalkPresum && NS > 1) {  // one part per lane row: index w0 / NS
+            if constexpr (NS > 1) {  // one part per lane row: index w0 / NS
                 double *dst = act ? B.sec_part + ((((size_t)(L.w0 / NS) * P.Nt) + k) * P.nvg + u) * L.nbe + L.be
                                   : reinterpret_cast<double *>(B.sink);
                 *dst = tot;
@@ -1511,24 +1392,13 @@ __global__ __launch_bounds__(kWalkBlock, 1) void k_walk_grad_pair(DevProblem P0,
 // gauge walks' own (walk_fwd_body / walk_grad_body with GAUGE): at equal chunking the results are
 // those of the per-class kernels bit for bit.  Both classes take class A's chunking (the engine
 // sets class B's L and nchunks to class A's).
-#ifndef GRAPE_WALK_MERGED_WAVES  // waves per SIMD of the merged gradient walk (222 VGPRs with E~ in registers)
-#define GRAPE_WALK_MERGED_WAVES 2
-#endif
-// E~ of the merged walks (round 6, GRAPE_WALK_FWD_ET_SMEM / GRAPE_WALK_GRAD_ET_SMEM): from the plan's
-// global copy (DevProblem::gauge_Et) through scalar loads -- E~ is launch-uniform, so each entry is an SGPR
-// operand of the complex product that forms E_k -- re-issued every step (the pointer is made opaque per
-// step, so the loads are not hoisted into 13 complex registers held across the walk).  The forward walk
-// then fits in 120 VGPRs (four waves per SIMD: fwd 0.161 -> 0.145 ms per C2 pass); the gradient walk would
-// fit in 160 (three waves) but measured slower there (0.308 -> 0.322 ms: the per-step scalar loads sit on
-// its critical path), so it keeps E~ from LDS in registers at two waves (A/B in one GPU call,
-// profiles/r06/ab_smem).  0: E~ in LDS (gauge_base_lds).  That is the matrix gradient walk; the rank-one
-// one (merged_step_grad_r1) is small enough for the scalar loads to win at three waves (GRAPE_WALK_R1_ET_SMEM).
-#ifndef GRAPE_WALK_FWD_ET_SMEM
-#define GRAPE_WALK_FWD_ET_SMEM 1
-#endif
-#ifndef GRAPE_WALK_GRAD_ET_SMEM
-#define GRAPE_WALK_GRAD_ET_SMEM 0
-#endif
+// E~ of the merged walks (round 6; SMEM of gauge_prop_lds): from the plan's global copy
+// (DevProblem::gauge_Et) through scalar loads -- E~ is launch-uniform, so each entry is an SGPR operand of the
+// complex product that forms E_k -- re-issued every step (the pointer is made opaque per step, so the loads are
+// not hoisted into 13 complex registers held across the walk).  The forward walks, the rank-one gradient walk
+// (merged_step_grad_r1) and the wide pass take E~ this way; the matrix gradient walk (merged_step_grad) keeps
+// E~ from LDS (gauge_base_lds) in registers at two waves, where the per-step scalar loads sat on its critical
+// path.
 template <int D, bool SMEM>
 __device__ __forceinline__ void gauge_prop_lds(const cd *Et, const cd (&e)[kGaugePairs<D>],
                                                MStore<D, false> &E) {  // gauge_prop, E~ in LDS or (SMEM) global
@@ -1563,7 +1433,7 @@ __global__ __launch_bounds__(64) void k_gauge_base_fill(DevProblem P, cd *scr, c
     SM<D> A[1];
     walk_build<D, 1>(P, as_constant(P.ops) + (size_t)w * P.sec_ops, X0, 1, none, A);
     double mu0 = 0.0;
-    walk_expm<D, false, true, false>(A[0], scr + (size_t)w * 2 * D * D, mu0, true, [&](int i, const cd (&x)[D]) {
+    walk_expm<D, false, false>(A[0], scr + (size_t)w * 2 * D * D, mu0, true, [&](int i, const cd (&x)[D]) {
 #pragma unroll
         for (int j = 0; j < D; ++j) out[(w * D + j) * D + i] = x[j];
     });
@@ -1576,7 +1446,7 @@ __device__ __forceinline__ void merged_step_fwd(const cd *Et, const GaugeN<D> (&
         if constexpr (LAD) gauge_phases_ladder<D>(p1, dph);
         else gauge_phases<D>(p1, gn[w], dph);
         MStore<D, false> E;
-        gauge_prop_lds<D, GRAPE_WALK_FWD_ET_SMEM>(Et + w * D * D, dph, E);
+        gauge_prop_lds<D, true>(Et + w * D * D, dph, E);
 #pragma unroll
         for (int i = 0; i < D; ++i) {  // column i of E_k Q (the forward walk's order)
             cd q[D], t[D];
@@ -1594,13 +1464,6 @@ __device__ __forceinline__ void merged_step_fwd(const cd *Et, const GaugeN<D> (&
         }
     }
 }
-#ifndef GRAPE_WALK_FWD_M_UNROLL  // the merged forward walk's main loop unrolled (loop-carried register moves)
-#define GRAPE_WALK_FWD_M_UNROLL 2  // (2: no loop-carried register moves, 2 waves/SIMD: fwd 0.183 -> 0.179 ms per C2 pass)
-#endif
-constexpr int kFwdMUnroll = GRAPE_WALK_FWD_M_UNROLL;
-#ifndef GRAPE_WALK_FWD_M_WAVES  // the merged forward walk (120 VGPRs with E~ in SGPRs: four waves fit)
-#define GRAPE_WALK_FWD_M_WAVES 4
-#endif
 // ---------------------------------------------------------------------------
 // The wide pass (round 8): one lane per evaluation over all N_t steps, no time chunks
 // ---------------------------------------------------------------------------
@@ -1659,12 +1522,6 @@ __device__ __forceinline__ void wide_store_u(cd *u, int c, const cd (&psi)[D]) {
         for (int i = 0; i < D; ++i) u[j * D + i] = i == c ? psi[j] : czero();
     }
 }
-#ifndef GRAPE_WALK_WIDE_FWD_WAVES  // the wide forward walk (10 VGPRs of state)
-#define GRAPE_WALK_WIDE_FWD_WAVES 4
-#endif
-#ifndef GRAPE_WALK_WIDE_GRAD_WAVES  // the wide gradient walk
-#define GRAPE_WALK_WIDE_GRAD_WAVES 4
-#endif
 // The controls of the workgroup's kWalkBlock evaluations over one tile of kFdxTile steps, [row][step] in LDS:
 // sixteen lanes read one row's 128-byte piece per instruction, so every line of x is fetched once and used
 // whole.  (A lane streaming its own row touches one line per lane and step and finds it evicted eight steps
@@ -1737,14 +1594,8 @@ __global__ __launch_bounds__(kWalkBlock, (WIDE ? GRAPE_WALK_WIDE_FWD_WAVES : GRA
     constexpr int NEB = TWB ? 1 : 2;
     const VBlock vb = hw_block();
     const WalkLane L = walk_lane<1>(PA, BA, vb);  // (class A: one sector; its chunking is both classes')
-    const double *xt = BA.xT + (size_t)L.be * (kWalkXRow ? PA.nx : 1);
-    const int xs = kWalkXRow ? 1 : L.nbe;
-    const cd *EtA = GRAPE_WALK_FWD_ET_SMEM
-                        ? PA.gauge_Et
-                        : gauge_base_lds<DA, 1>(PA, as_constant(PA.ops), BA.wscr + (size_t)L.slot * 2 * DA * DA);
-    const cd *EtB = GRAPE_WALK_FWD_ET_SMEM
-                        ? PB.gauge_Et
-                        : gauge_base_lds<2, NEB>(PB, as_constant(PB.ops), BB.wscr + (size_t)L.slot * 2 * 2 * 4);
+    const double *xt = BA.xT + (size_t)L.be * PA.nx;  // this evaluation's row of x (B.xT = B.x)
+    const cd *EtA = PA.gauge_Et, *EtB = PB.gauge_Et;  // (through scalar loads: gauge_prop_lds)
     GaugeN<DA> gA[1];
     GaugeN<2> gB[NEB];
     gA[0] = gauge_charges<DA>(PA, 0);
@@ -1765,11 +1616,11 @@ __global__ __launch_bounds__(kWalkBlock, (WIDE ? GRAPE_WALK_WIDE_FWD_WAVES : GRA
         }
     }
     const int k0 = L.c * PA.L;
-    X2 xn = walk_load_x(1, xt + (size_t)min(k0, PA.Nt - 1) * xs, xs);
+    X2 xn = walk_load_x(1, xt + (size_t)min(k0, PA.Nt - 1));
     auto step = [&](int jj) {
         const int k = min(k0 + jj, PA.Nt - 1);
         const double xk = xn.v0;
-        xn = walk_load_x(1, xt + (size_t)min(k + 1, PA.Nt - 1) * xs, xs);  // next step's control
+        xn = walk_load_x(1, xt + (size_t)min(k + 1, PA.Nt - 1));  // next step's control
         const cd p1 = gauge_cis(PA.gauge_a * xk);  // e^{i a x_k}, both classes (the engine checks one a)
         merged_step_fwd<DA, 1, LAD>(EtA, gA, p1, QA);
         merged_step_fwd<2, NEB, LAD>(EtB, gB, p1, QB);
@@ -1777,16 +1628,13 @@ __global__ __launch_bounds__(kWalkBlock, (WIDE ? GRAPE_WALK_WIDE_FWD_WAVES : GRA
     // steps past N_t leave Q alone: only the last chunk has them, so the first n_last steps of every
     // chunk run unpredicated and the rest only in the other chunks' lanes (a branch, not selects)
     const int nlast = PA.Nt - (PA.nchunks - 1) * PA.L;
-    // unrolled by hand (two steps per trip, then the odd one): the phases' constants pass through an
-    // inline asm (gauge_cis), which LLVM treats as convergent and will not runtime-unroll
-    static_assert(kFwdMUnroll == 1 || kFwdMUnroll == 2, "GRAPE_WALK_FWD_M_UNROLL: 1 or 2");
+    // unrolled by hand (two steps per trip, then the odd one: no loop-carried register moves): the phases'
+    // constants pass through an inline asm (gauge_cis), which LLVM treats as convergent and will not runtime-unroll
     int j2 = 0;
-    if constexpr (kFwdMUnroll == 2) {
 #pragma unroll 1
-        for (; j2 + 1 < nlast; j2 += 2) {
-            step(j2);
-            step(j2 + 1);
-        }
+    for (; j2 + 1 < nlast; j2 += 2) {
+        step(j2);
+        step(j2 + 1);
     }
 #pragma unroll 1
     for (; j2 < nlast; ++j2) step(j2);
@@ -1928,26 +1776,18 @@ __device__ __forceinline__ void merged_xinit(const cd *Cr, const cd *Mw, cd (&X)
 }
 // one gradient step of NSEC sectors over NE propagators (NSH = NSEC / NE sectors share one):
 // Y = X E^dag, the contraction, X <- E Y; returns the sectors' terms summed in sector order
-// (kWalkPresum: (0 + s_0) + s_1 ...; one sector: s_0)
-#ifndef GRAPE_WALK_LADDER_CONTR  // ladder classes: the contraction grouped by charge difference (below)
-#define GRAPE_WALK_LADDER_CONTR 1
-#endif
+// ((0 + s_0) + s_1 ...; one sector: s_0)
 template <int D, int NE, int NSEC, bool LAD>
 __device__ __forceinline__ double merged_step_grad(const cd *Et, const GaugeN<D> (&gn)[NE], cd p1, cd q,
                                                    double inv_eps, cd (&X)[NSEC][D][D]) {
     constexpr int NSH = NSEC / NE;
     MStore<D, false> E[NE];
-    cd rho[NE][D];
 #pragma unroll
     for (int w = 0; w < NE; ++w) {
         cd dph[kGaugePairs<D>];
         if constexpr (LAD) gauge_phases_ladder<D>(p1, dph);
         else gauge_phases<D>(p1, gn[w], dph);
-        gauge_prop_lds<D, GRAPE_WALK_GRAD_ET_SMEM>(Et + w * D * D, dph, E[w]);
-#if !GRAPE_GAUGE_FD_DN
-#pragma unroll
-        for (int j = 0; j < D; ++j) rho[w][j] = gauge_rho(q, gn[w].n[j]);
-#endif
+        gauge_prop_lds<D, false>(Et + w * D * D, dph, E[w]);
     }
 #pragma unroll
     for (int w = 0; w < NSEC; ++w) {  // Y = X E^dag, row by row
@@ -2021,11 +1861,7 @@ __device__ __forceinline__ double merged_step_grad(const cd *Et, const GaugeN<D>
 #pragma unroll
         for (int t = 0; t < NSH; ++t) s[t] = 0.0;
         cd fw[kGaugePairs<D>];
-#if GRAPE_GAUGE_FD_DN
         gauge_fd_weights_dn<D>(q, gn[we], fw);
-#else
-        gauge_fd_weights<D>(rho[we], fw);
-#endif
 #pragma unroll
         for (int r = 0; r < D; ++r) {
 #pragma unroll
@@ -2066,7 +1902,7 @@ __device__ __forceinline__ double merged_step_grad(const cd *Et, const GaugeN<D>
             for (int j = 0; j < D; ++j) X[w][j][i] = t[j];
         }
     }
-    return (kWalkPresum && NSEC > 1) ? tot : one;
+    return NSEC > 1 ? tot : one;
 }
 // The rank-one gradient step (R1, DevProblem::rank1).  With the diagonal head every sector's M block has
 // one non-zero row, M = e_c m^T (grape_projector.hip diag_row: row r carries the factor W[g_r]), so
@@ -2078,16 +1914,9 @@ __device__ __forceinline__ double merged_step_grad(const cd *Et, const GaugeN<D>
 // Per 3-level sector and step: 36 FMA (phi) + 18 MUL + 18 FMA (u) + 24 FMA (T) + 12 ADD (psi), where the
 // matrix step spends 216 FMA on its two products and 24 on the contraction.
 // Its registers (24 VGPRs of state where the matrix walk holds 36, no Y) leave room for a third wave per SIMD once
-// E~ comes through scalar loads (GRAPE_WALK_R1_ET_SMEM: 108 VGPRs, no scratch; with E~ from LDS in registers the
-// lane spills at three waves), and there the scalar loads pay: C2 72.0-73.0 M evals/s at two waves with E~ from
-// LDS, 70.3-73.3 M at three (spilling), 77.9-78.3 M at three with scalar loads, 77.0-77.8 M at four (A/B in one GPU
-// call).  The matrix walk keeps GRAPE_WALK_MERGED_WAVES / GRAPE_WALK_GRAD_ET_SMEM.
-#ifndef GRAPE_WALK_R1_WAVES
-#define GRAPE_WALK_R1_WAVES 3
-#endif
-#ifndef GRAPE_WALK_R1_ET_SMEM
-#define GRAPE_WALK_R1_ET_SMEM 1
-#endif
+// E~ comes through scalar loads (108 VGPRs, no scratch; with E~ from LDS in registers the
+// lane spills at three waves), and there the scalar loads pay.  The matrix walk keeps
+// GRAPE_WALK_MERGED_WAVES and E~ from LDS.
 template <int D, int NE, int NSEC, bool LAD>
 __device__ __forceinline__ double merged_step_grad_r1(const cd *Et, const GaugeN<D> (&gn)[NE], cd p1, cd q,
                                                       double inv_eps, cd (&psi)[NSEC][D], cd (&phi)[NSEC][D]) {
@@ -2098,7 +1927,7 @@ __device__ __forceinline__ double merged_step_grad_r1(const cd *Et, const GaugeN
         cd dph[kGaugePairs<D>];
         if constexpr (LAD) gauge_phases_ladder<D>(p1, dph);
         else gauge_phases<D>(p1, gn[w], dph);
-        gauge_prop_lds<D, GRAPE_WALK_R1_ET_SMEM>(Et + w * D * D, dph, E[w]);
+        gauge_prop_lds<D, true>(Et + w * D * D, dph, E[w]);
     }
     cd rh[D];
     if constexpr (LAD) ladder_rho<D>(q, rh);
@@ -2107,14 +1936,7 @@ __device__ __forceinline__ double merged_step_grad_r1(const cd *Et, const GaugeN
     for (int we = 0; we < NE; ++we) {
         cd fw[kGaugePairs<D>];
         if constexpr (!LAD) {
-#if GRAPE_GAUGE_FD_DN
             gauge_fd_weights_dn<D>(q, gn[we], fw);
-#else
-            cd rho[D];
-#pragma unroll
-            for (int j = 0; j < D; ++j) rho[j] = gauge_rho(q, gn[we].n[j]);
-            gauge_fd_weights<D>(rho, fw);
-#endif
         }
 #pragma unroll
         for (int t = 0; t < NSH; ++t) {
@@ -2184,14 +2006,8 @@ __device__ __forceinline__ double merged_step_grad_r1(const cd *Et, const GaugeN
             }
         }
     }
-    return (kWalkPresum && NSEC > 1) ? tot : one;
+    return NSEC > 1 ? tot : one;
 }
-#ifndef GRAPE_WALK_TWIN_SUM  // merged gradient walk, twin class B: one summed state for both sectors
-#define GRAPE_WALK_TWIN_SUM 1
-#endif
-#ifndef GRAPE_WALK_MERGED_FDX  // the merged gradient walk writes F_dx itself (1) or a part for k_sec_reduce (0)
-#define GRAPE_WALK_MERGED_FDX 1
-#endif
 // the rank-one walk's chunk start of one sector: psi = Carry e_c, phi = Carry conj(m), m = row c of the sector's M
 // block (of the twins' summed block: Mw2).  c is launch-uniform and enters addresses only.
 template <int D>
@@ -2233,14 +2049,7 @@ __device__ __forceinline__ double wide_step_grad(const cd *Et, const GaugeN<D> (
     for (int we = 0; we < NE; ++we) {
         cd fw[kGaugePairs<D>];
         if constexpr (!LAD) {
-#if GRAPE_GAUGE_FD_DN
             gauge_fd_weights_dn<D>(q, gn[we], fw);
-#else
-            cd rho[D];
-#pragma unroll
-            for (int j = 0; j < D; ++j) rho[j] = gauge_rho(q, gn[we].n[j]);
-            gauge_fd_weights<D>(rho, fw);
-#endif
         }
 #pragma unroll
         for (int t = 0; t < NSH; ++t) {
@@ -2310,7 +2119,7 @@ __device__ __forceinline__ double wide_step_grad(const cd *Et, const GaugeN<D> (
             }
         }
     }
-    return (kWalkPresum && NSEC > 1) ? tot : one;
+    return NSEC > 1 ? tot : one;
 }
 // the wide gradient walk's start of one sector: psi_N = column c of the head's U block, phi_N = conj(alpha) e_c
 // (alpha: the head's factor of row c of M, grape_projector.hip diag_row; summed over a twin pair: a2)
@@ -2378,7 +2187,7 @@ template <int DA, bool TWB, bool LAD, bool R1, bool WIDE = false>
 __global__ __launch_bounds__(kWalkBlock, (WIDE ? GRAPE_WALK_WIDE_GRAD_WAVES : R1 ? GRAPE_WALK_R1_WAVES : GRAPE_WALK_MERGED_WAVES)) void k_walk_grad_m(DevProblem PA, DevBatch BA,
                                                                                    DevProblem PB, DevBatch BB, int a_first) {
     constexpr int NEB = TWB ? 1 : 2;
-    __shared__ double ftile[kWalkBlock][kFdxTile + 1];  // (GRAPE_WALK_MERGED_FDX; +1: conflict-free rows)
+    __shared__ double ftile[kWalkBlock][kFdxTile + 1];  // (the F_dx tile; +1: conflict-free rows)
     __shared__ int2 frow[kWalkBlock];                   // each row's evaluation and first step
     if constexpr (WIDE) {
         wide_grad_body<DA, TWB, LAD>(PA, BA, PB, BB, a_first, ftile, frow);
@@ -2386,9 +2195,8 @@ __global__ __launch_bounds__(kWalkBlock, (WIDE ? GRAPE_WALK_WIDE_GRAD_WAVES : R1
     }
     const VBlock vb = hw_block();
     const WalkLane L = walk_lane<1>(PA, BA, vb);
-    const double *xt = BA.xT + (size_t)L.be * (kWalkXRow ? PA.nx : 1);
-    const int xs = kWalkXRow ? 1 : L.nbe;
-    if constexpr (GRAPE_WALK_MERGED_FDX) frow[threadIdx.x] = make_int2(L.ok ? L.be : -1, L.c * PA.L);
+    const double *xt = BA.xT + (size_t)L.be * PA.nx;  // this evaluation's row of x (B.xT = B.x)
+    frow[threadIdx.x] = make_int2(L.ok ? L.be : -1, L.c * PA.L);
     // Twin class B (one propagator for both sectors): X_w <- E X_w E^dag is linear and the lane sums
     // the sectors' terms, so ONE state X = Carry (M_00 + M_11) Carry^dag carries both (GRAPE_WALK_TWIN_SUM:
     // half of class B's products; the sectors' sum formed once instead of per step -- rounding only)
@@ -2425,24 +2233,22 @@ __global__ __launch_bounds__(kWalkBlock, (WIDE ? GRAPE_WALK_WIDE_GRAD_WAVES : R1
             merged_xinit<2>(Cb, Mb, XB[w]);
         }
     }
-    constexpr bool ET_SMEM = R1 ? GRAPE_WALK_R1_ET_SMEM : GRAPE_WALK_GRAD_ET_SMEM;
-    const cd *EtA = ET_SMEM
-                        ? PA.gauge_Et
-                        : gauge_base_lds<DA, 1>(PA, as_constant(PA.ops), BA.wscr + (size_t)L.slot * 2 * DA * DA);
-    const cd *EtB = ET_SMEM
-                        ? PB.gauge_Et
-                        : gauge_base_lds<2, NEB>(PB, as_constant(PB.ops), BB.wscr + (size_t)L.slot * 2 * 2 * 4);
+    // E~: the rank-one walk's through scalar loads, the matrix walk's from LDS (gauge_prop_lds)
+    const cd *EtA = R1 ? PA.gauge_Et
+                       : gauge_base_lds<DA, 1>(PA, as_constant(PA.ops), BA.wscr + (size_t)L.slot * 2 * DA * DA);
+    const cd *EtB = R1 ? PB.gauge_Et
+                       : gauge_base_lds<2, NEB>(PB, as_constant(PB.ops), BB.wscr + (size_t)L.slot * 2 * 2 * 4);
     GaugeN<DA> gA[1];
     GaugeN<2> gB[NEB];
     gA[0] = gauge_charges<DA>(PA, 0);
 #pragma unroll
     for (int w = 0; w < NEB; ++w) gB[w] = gauge_charges<2>(PB, w);
     const int k0 = L.c * PA.L;
-    X2 xn = walk_load_x(1, xt + (size_t)min(k0, PA.Nt - 1) * xs, xs);
+    X2 xn = walk_load_x(1, xt + (size_t)min(k0, PA.Nt - 1));
     auto step = [&](int jj) {  // one step of both classes: the F_dx value, in the plan's class order
         const int k = min(k0 + jj, PA.Nt - 1);
         const double xk = xn.v0, xe = xk + PA.eps;  // the reference's perturbed control
-        xn = walk_load_x(1, xt + (size_t)min(k + 1, PA.Nt - 1) * xs, xs);  // next step's control
+        xn = walk_load_x(1, xt + (size_t)min(k + 1, PA.Nt - 1));  // next step's control
         const cd p1 = gauge_cis(PA.gauge_a * xk), q = cis_m1(PA.gauge_a * (xe - xk));  // (xe - xk: exact)
         double sa, sb;
         if constexpr (R1) {
@@ -2457,34 +2263,23 @@ __global__ __launch_bounds__(kWalkBlock, (WIDE ? GRAPE_WALK_WIDE_GRAD_WAVES : R1
         v += a_first ? sb : sa;
         return v;
     };
-    if constexpr (GRAPE_WALK_MERGED_FDX) {
-        // F_dx straight to its [evaluation][n_x] row through a workgroup tile of kFdxTile steps: the
-        // lanes of a workgroup hold consecutive evaluations, so a flush writes 16 lanes' kFdxTile-long
-        // row pieces per instruction (no part array, no k_sec_reduce).  Uniform trip counts: every
-        // lane reaches the barriers; steps past N_t are walked and not stored.
+    // F_dx straight to its [evaluation][n_x] row through a workgroup tile of kFdxTile steps: the
+    // lanes of a workgroup hold consecutive evaluations, so a flush writes 16 lanes' kFdxTile-long
+    // row pieces per instruction (no part array, no k_sec_reduce).  Uniform trip counts: every
+    // lane reaches the barriers; steps past N_t are walked and not stored.
 #pragma unroll 1
-        for (int j0 = 0; j0 < PA.L; j0 += kFdxTile) {
-            const int nj = min(kFdxTile, PA.L - j0);
+    for (int j0 = 0; j0 < PA.L; j0 += kFdxTile) {
+        const int nj = min(kFdxTile, PA.L - j0);
 #pragma unroll 1  // (unrolled by 2: the same instructions per step)
-            for (int t = 0; t < nj; ++t) ftile[threadIdx.x][t] = step(j0 + t);
-            __syncthreads();
-            const int j = threadIdx.x % kFdxTile;
+        for (int t = 0; t < nj; ++t) ftile[threadIdx.x][t] = step(j0 + t);
+        __syncthreads();
+        const int j = threadIdx.x % kFdxTile;
 #pragma unroll 1
-            for (int row = threadIdx.x / kFdxTile; row < kWalkBlock; row += kWalkBlock / kFdxTile) {
-                const int br = frow[row].x, kk = frow[row].y + j0 + j;  // (br < 0: past the last lane)
-                if (j < nj && br >= 0 && kk < PA.Nt) BA.Fdx[(size_t)br * PA.nx + kk] = ftile[row][j];
-            }
-            __syncthreads();
+        for (int row = threadIdx.x / kFdxTile; row < kWalkBlock; row += kWalkBlock / kFdxTile) {
+            const int br = frow[row].x, kk = frow[row].y + j0 + j;  // (br < 0: past the last lane)
+            if (j < nj && br >= 0 && kk < PA.Nt) BA.Fdx[(size_t)br * PA.nx + kk] = ftile[row][j];
         }
-    } else {
-#pragma unroll 1
-        for (int jj = 0; jj < PA.L; ++jj) {
-            const int k = min(k0 + jj, PA.Nt - 1);
-            const bool act = L.ok && k0 + jj < PA.Nt;
-            const double v = step(jj);
-            double *dst = act ? BA.sec_part + (size_t)k * L.nbe + L.be : reinterpret_cast<double *>(BA.sink);
-            *dst = v;
-        }
+        __syncthreads();
     }
 }
 
@@ -2549,8 +2344,7 @@ __global__ __launch_bounds__(kWalkBlock, (WalkCfg<D, NS>::WAVES_IMG)) void k_wal
     const WalkLane L = walk_lane<NS>(P, B, vb);
     const size_t lanes = (size_t)vb.gx * kWalkBlock, lane = (size_t)vb.x * kWalkBlock + threadIdx.x;
     const int ns = P.nsec > 1 ? P.nsec : 1;
-    const double *xt = B.xT + (size_t)L.be * (kWalkXRow ? P.nx : 1);  // x[q] of this evaluation at xt[q * xs]
-    const int xs = kWalkXRow ? 1 : L.nbe;
+    const double *xt = B.xT + (size_t)L.be * P.nx;  // this evaluation's row of x (B.xT = B.x)
     const cptr<cd> ops = as_constant(P.ops) + (size_t)L.w0 * P.sec_ops;
     const cptr<VSpec> vs = as_constant(P.vs);
     cd *scr = B.wscr + (size_t)L.slot * NS * 2 * TS;
@@ -2559,9 +2353,9 @@ __global__ __launch_bounds__(kWalkBlock, (WalkCfg<D, NS>::WAVES_IMG)) void k_wal
     none.index = 0;
     none.delta = 0.0;
     WalkX X;
-    walk_set_xa(X, walk_load_x(P.na, xt + (size_t)P.np * P.Nt * xs, xs));  // x_add
+    walk_set_xa(X, walk_load_x(P.na, xt + (size_t)P.np * P.Nt));  // x_add
     const int k0 = L.c * P.L;
-    X2 xn = walk_load_x(P.np, xt + (size_t)min(k0, P.Nt - 1) * P.np * xs, xs);
+    X2 xn = walk_load_x(P.np, xt + (size_t)min(k0, P.Nt - 1) * P.np);
     // Q_{k-1} (chunk-local), E_k, and the step's eps2 propagators E(x + eps2), E(err_e eps2) (the
     // latter two in the lane's LDS slots at D = 4, where the registers run out)
     cd Q[NS][D][D], E[NS][D][D];
@@ -2569,15 +2363,6 @@ __global__ __launch_bounds__(kWalkBlock, (WalkCfg<D, NS>::WAVES_IMG)) void k_wal
     double mu[NS];  // this step's diagonal shifts (every variant takes the nominal's)
     constexpr bool EL = C::IMG_LDS;
     MStore<D, EL> Ed2[NS], Ee2[NS];
-    // W chunk sums in LDS (IMG_WSUM): entry (e, t) of this lane at wacc[(e * TS + t) * kWalkBlock]
-    const bool ws = C::IMG_WSUM && P.ne <= kWsumMaxE;
-    cd *wacc = nullptr;
-    if constexpr (C::IMG_WSUM) {
-        __shared__ cd lds_w[kWalkBlock * kWsumMaxE * TS];
-        wacc = lds_w + threadIdx.x;
-#pragma unroll
-        for (int t = 0; t < kWsumMaxE * TS; ++t) wacc[t * kWalkBlock] = czero();
-    }
     if constexpr (EL) {
         static_assert(NS == 1, "one pair of LDS slots per lane");
         __shared__ cd lds_d2[kWalkBlock * MStore<D, true>::kStride], lds_e2[kWalkBlock * MStore<D, true>::kStride];
@@ -2597,13 +2382,13 @@ __global__ __launch_bounds__(kWalkBlock, (WalkCfg<D, NS>::WAVES_IMG)) void k_wal
         const int k = min(k0 + jj, P.Nt - 1);
         const bool act = L.ok && k0 + jj < P.Nt;
         walk_set_xk(X, xn);
-        xn = walk_load_x(P.np, xt + (size_t)min(k + 1, P.Nt - 1) * P.np * xs, xs);  // next step's controls
+        xn = walk_load_x(P.np, xt + (size_t)min(k + 1, P.Nt - 1) * P.np);  // next step's controls
         {
             SM<D> A[NS];
             walk_build<D, NS>(P, ops, X, k + 1, none, A);
 #pragma unroll
             for (int w = 0; w < NS; ++w) {
-                walk_expm<D, C::FENCE, true, C::SHIFT>(A[w], scr + (size_t)w * 2 * TS, mu[w], true, [&](int i, const cd (&x)[D]) {
+                walk_expm<D, C::FENCE, C::SHIFT>(A[w], scr + (size_t)w * 2 * TS, mu[w], true, [&](int i, const cd (&x)[D]) {
 #pragma unroll
                     for (int j = 0; j < D; ++j) E[w][j][i] = x[j];
                 });
@@ -2619,7 +2404,7 @@ __global__ __launch_bounds__(kWalkBlock, (WalkCfg<D, NS>::WAVES_IMG)) void k_wal
 #pragma unroll
             for (int w = 0; w < NS; ++w) {
                 if constexpr (KIND == IMG_KEEP_D2 || KIND == IMG_KEEP_E2) {
-                    walk_expm<D, C::FENCE, C::KEEP_A2_IMG, C::SHIFT>(A[w], scr + (size_t)w * 2 * TS, mu[w], false, [&](int i, const cd (&x)[D]) {
+                    walk_expm<D, C::FENCE, C::SHIFT>(A[w], scr + (size_t)w * 2 * TS, mu[w], false, [&](int i, const cd (&x)[D]) {
 #pragma unroll
                         for (int j = 0; j < D; ++j) {
                             if constexpr (KIND == IMG_KEEP_D2) Ed2[w].set(j, i, x[j]);
@@ -2628,7 +2413,7 @@ __global__ __launch_bounds__(kWalkBlock, (WalkCfg<D, NS>::WAVES_IMG)) void k_wal
                     });
                 } else {
                     cd Z[D][D];  // E_k^dag dX, column by column as the variant's columns come out
-                    walk_expm<D, C::FENCE, C::KEEP_A2_IMG, C::SHIFT>(A[w], scr + (size_t)w * 2 * TS, mu[w], false, [&](int i, const cd (&x)[D]) {
+                    walk_expm<D, C::FENCE, C::SHIFT>(A[w], scr + (size_t)w * 2 * TS, mu[w], false, [&](int i, const cd (&x)[D]) {
                         cd dx[D];
                         const auto &e2 = Ee2[w].opaque();  // (LDS reads issued here, not hoisted)
                         const auto &d2 = Ed2[w].opaque();
@@ -2665,12 +2450,6 @@ __global__ __launch_bounds__(kWalkBlock, (WalkCfg<D, NS>::WAVES_IMG)) void k_wal
 #pragma unroll
                             for (int m = 0; m < D; ++m) cmac(c, cconj(Q[w][m][r]), t[m]);
                             dst[(size_t)(r * D + cc) * lanes] = c;
-                            if constexpr (C::IMG_WSUM && KIND == IMG_DIFF) {  // W_e: the chunk sum, in step order
-                                if (ws && act && slot >= P.nvg) {
-                                    cd &a = wacc[((slot - P.nvg) * TS + r * D + cc) * kWalkBlock];
-                                    a = cadd(a, c);
-                                }
-                            }
                         }
                     }
                 }
@@ -2710,17 +2489,6 @@ __global__ __launch_bounds__(kWalkBlock, (WalkCfg<D, NS>::WAVES_IMG)) void k_wal
 #pragma unroll
                 for (int j = 0; j < D; ++j)
                     Q[w][j][i] = cmake(act ? t[j].re : Q[w][j][i].re, act ? t[j].im : Q[w][j][i].im);
-            }
-        }
-    }
-    if constexpr (C::IMG_WSUM) {
-        if (ws && L.ok) {  // B.Wc [sub-evaluation][ne][nchunks][D][D] (k_walk_img_sum's layout and sums)
-            const size_t sub = (size_t)L.be * ns + L.w0;
-#pragma unroll 1
-            for (int e = 0; e < P.ne; ++e) {
-                cd *dst = B.Wc + ((sub * P.ne + e) * P.nchunks + L.c) * TS;
-#pragma unroll
-                for (int t = 0; t < TS; ++t) dst[t] = wacc[(e * TS + t) * kWalkBlock];
             }
         }
     }
@@ -2770,8 +2538,7 @@ __global__ __launch_bounds__(kWalkBlock, (img_gauge_waves<D, NS>())) void k_walk
     const WalkLane L = walk_lane<NS>(P, B, vb);
     const size_t lanes = (size_t)vb.gx * kWalkBlock, lane = (size_t)vb.x * kWalkBlock + threadIdx.x;
     const int ns = P.nsec > 1 ? P.nsec : 1, NE = P.ne;
-    const double *xt = B.xT + (size_t)L.be * (kWalkXRow ? P.nx : 1);
-    const int xs = kWalkXRow ? 1 : L.nbe;
+    const double *xt = B.xT + (size_t)L.be * P.nx;  // this evaluation's row of x (B.xT = B.x)
     __shared__ cd gbase[NS * NBM * TS];
     // --- the workgroup's x-independent bases: lane t < NS (1 + 2 NE) computes matrix (w, b) ---
     {
@@ -2790,7 +2557,7 @@ __global__ __launch_bounds__(kWalkBlock, (img_gauge_waves<D, NS>())) void k_walk
             walk_build<D, 1>(P, as_constant(P.ops) + (size_t)(L.w0 + w) * P.sec_ops, X0, 1, none, A, e, ev);
             double mu0 = 0.0;
             cd *dst = img_gauge_base<D, NS>(gbase, w, b);
-            walk_expm<D, false, true, false>(A[0], B.wscr + (size_t)L.slot * NS * 2 * TS, mu0, true,
+            walk_expm<D, false, false>(A[0], B.wscr + (size_t)L.slot * NS * 2 * TS, mu0, true,
                                              [&](int i, const cd (&x)[D]) {
 #pragma unroll
                                                  for (int j = 0; j < D; ++j) dst[j * D + i] = x[j];
@@ -2831,7 +2598,7 @@ __global__ __launch_bounds__(kWalkBlock, (img_gauge_waves<D, NS>())) void k_walk
 #pragma unroll
     for (int w = 0; w < NS; ++w) gn[w] = gauge_charges<D>(P, L.w0 + w);
     const int k0 = L.c * P.L;
-    X2 xn = walk_load_x(1, xt + (size_t)min(k0, P.Nt - 1) * xs, xs);
+    X2 xn = walk_load_x(1, xt + (size_t)min(k0, P.Nt - 1));
     cd Q[NS][D][D];
 #pragma unroll
     for (int w = 0; w < NS; ++w) {
@@ -2846,28 +2613,15 @@ __global__ __launch_bounds__(kWalkBlock, (img_gauge_waves<D, NS>())) void k_walk
         const int k = min(k0 + jj, P.Nt - 1);
         const bool act = L.ok && k0 + jj < P.Nt;
         const double xk = xn.v0;
-        xn = walk_load_x(1, xt + (size_t)min(k + 1, P.Nt - 1) * xs, xs);  // next step's control
+        xn = walk_load_x(1, xt + (size_t)min(k + 1, P.Nt - 1));  // next step's control
         const cd p1 = gauge_cis(P.gauge_a * xk);
         const cd q1 = cis_m1(P.gauge_a * ((xk + P.eps) - xk)), q2 = cis_m1(P.gauge_a * ((xk + P.eps2) - xk));
 #pragma unroll
         for (int w = 0; w < NS; ++w) {
             cd d[kGaugePairs<D>], f1[kGaugePairs<D>], f2[kGaugePairs<D>];
             gauge_phases<D>(p1, gn[w], d);
-#if GRAPE_GAUGE_FD_DN
             gauge_fd_weights_dn<D>(q1, gn[w], f1);
             gauge_fd_weights_dn<D>(q2, gn[w], f2);
-#else
-            {
-                cd r1[D], r2[D];
-#pragma unroll
-                for (int j = 0; j < D; ++j) {
-                    r1[j] = gauge_rho(q1, gn[w].n[j]);
-                    r2[j] = gauge_rho(q2, gn[w].n[j]);
-                }
-                gauge_fd_weights<D>(r1, f1);
-                gauge_fd_weights<D>(r2, f2);
-            }
-#endif
             const cd *E0 = img_gauge_base<D, NS>(gbase, w, 0);
             // image of slot: Y = Q^dag (D Zt D^dag) Q, Zt given row-major (scaled by `sc`)
             auto emit = [&](const cd (&Zt)[D][D], int slot, double sc) {
@@ -2976,17 +2730,10 @@ __global__ __launch_bounds__(kWalkBlock, (img_gauge_waves<D, NS>())) void k_walk
 // ---------------------------------------------------------------------------
 // The image walk's back end (error sources, walk path): walks over the lane-minor images
 // ---------------------------------------------------------------------------
-// Stage 1, k_walk_img_sum: one lane per (chunk c, evaluation) as the image walk, its NS sectors:
-//   F_dx[u, k] (sector part) = Re tr(M'_c Z1_u)          (FidelityCalculations.jl:56-76)
-// written lane-major (B.sec_part, [nsec][Nt][nvg][nbe], as k_walk_grad), and the chunk sums of the
-// error images sum_{k in c} W_{e,k} to B.Wc ([sub-evaluation][ne][nchunks][D][D], row-major tiles:
-// Phase A of k_err_scan, UnitaryCalculations.jl:112).  One read of Z1 and of every W per step.
-// GRAPE_WALK_FDX_IN_ERR (default): the F_dx traces are taken by k_walk_err_grad's e = 0 lanes, which
-// read Z1 anyway, so this kernel reads only the W images (C3: 5 -> 4 of the 9 tiles per step), and
-// not at all for the 2-level classes whose image walk sums W itself (WalkCfg::IMG_WSUM).
-#ifndef GRAPE_WALK_IMGSUM_UNROLL
-#define GRAPE_WALK_IMGSUM_UNROLL 1
-#endif
+// Stage 1, k_walk_img_sum: one lane per (chunk c, evaluation) as the image walk, its NS sectors: the chunk
+// sums of the error images sum_{k in c} W_{e,k} to B.Wc ([sub-evaluation][ne][nchunks][D][D], row-major tiles:
+// Phase A of k_err_scan, UnitaryCalculations.jl:112).  It reads only the W images (C3: 4 of the 9 tiles per
+// step): the F_dx traces Re tr(M'_c Z1_u) are taken by k_walk_err_grad's e = 0 lanes, which read Z1 anyway.
 template <int D, int NS>
 __global__ __launch_bounds__(kWalkBlock, 2) void k_walk_img_sum(DevProblem P, DevBatch B) {
     constexpr int TS = D * D;
@@ -2998,57 +2745,23 @@ __global__ __launch_bounds__(kWalkBlock, 2) void k_walk_img_sum(DevProblem P, De
 #pragma unroll
     for (int w = 0; w < NS; ++w) {
         const size_t sub = (size_t)L.be * ns + L.w0 + w;
-#if !GRAPE_WALK_FDX_IN_ERR
-        cd Mt[TS];  // M'_c, row-major
-        const cd *Mc = B.Mc + (sub * P.nchunks + L.c) * TS;
-#pragma unroll
-        for (int t = 0; t < TS; ++t) Mt[t] = Mc[t];
-#pragma unroll 1
-        for (int u = 0; u < P.nvg; ++u) {
-#pragma unroll 1
-            for (int jj = 0; jj < P.L; ++jj) {
-                const int k = k0 + jj;
-                const cd *Z = B.Zl + img_index<D, NS>(P, vb.y, jj, w, u, 0, lanes, lane);
-                double s = 0.0;  // sum_ij Re(Z1[i][j] M'[j][i]) in k_img_fdx's (round 3) order
-#pragma unroll
-                for (int i = 0; i < D; ++i) {
-#pragma unroll
-                    for (int j = 0; j < D; ++j) {
-                        const cd z = Z[(size_t)(i * D + j) * lanes], m = Mt[j * D + i];
-                        s += z.re * m.re - z.im * m.im;
-                    }
-                }
-                double *dst = (L.ok && k < P.Nt)
-                                  ? B.sec_part + ((((size_t)(L.w0 + w) * P.Nt) + k) * P.nvg + u) * L.nbe + L.be
-                                  : reinterpret_cast<double *>(B.sink);
-                *dst = s;
-            }
-        }
-#endif
 #pragma unroll 1
         for (int e = 0; e < P.ne; ++e) {
             cd acc[TS];
 #pragma unroll
             for (int t = 0; t < TS; ++t) acc[t] = czero();
-            // GRAPE_WALK_IMGSUM_UNROLL steps per iteration, loads unconditional (the step index
-            // clamped), so their reads are in flight together; the sums stay in step order
-            constexpr int UN = GRAPE_WALK_IMGSUM_UNROLL;
 #pragma unroll 1
-            for (int j0 = 0; j0 < P.L; j0 += UN) {
-                cd v[UN][TS];
+            for (int jj = 0; jj < P.L; ++jj) {  // the sums in step order; steps past N_t add nothing
+                cd v[TS];
+                // (min: it clamps nothing for jj < P.L -- left from the form that loaded several steps per trip,
+                // because the compiler does not see that and schedules the kernel differently without it.  To go
+                // once the kernels no longer have to be the round-8 machine code: DESIGN.md 10)
+                const cd *Wk = B.Zl + img_index<D, NS>(P, vb.y, min(jj, P.L - 1), w, P.nvg + e, 0, lanes, lane);
 #pragma unroll
-                for (int du = 0; du < UN; ++du) {
-                    const int jj = min(j0 + du, P.L - 1);
-                    const cd *Wk = B.Zl + img_index<D, NS>(P, vb.y, jj, w, P.nvg + e, 0, lanes, lane);
+                for (int t = 0; t < TS; ++t) v[t] = Wk[(size_t)t * lanes];
+                const bool act = k0 + jj < P.Nt;  // (uniform within a chunk's lanes)
 #pragma unroll
-                    for (int t = 0; t < TS; ++t) v[du][t] = Wk[(size_t)t * lanes];
-                }
-#pragma unroll
-                for (int du = 0; du < UN; ++du) {
-                    const bool act = j0 + du < P.L && k0 + j0 + du < P.Nt;  // (uniform within a chunk's lanes)
-#pragma unroll
-                    for (int t = 0; t < TS; ++t) acc[t] = act ? cadd(acc[t], v[du][t]) : acc[t];
-                }
+                for (int t = 0; t < TS; ++t) acc[t] = act ? cadd(acc[t], v[t]) : acc[t];
             }
             if (L.ok) {
                 cd *dst = B.Wc + ((sub * P.ne + e) * P.nchunks + L.c) * TS;
@@ -3117,14 +2830,12 @@ __global__ __launch_bounds__(kWalkBlock, (D >= 4 ? 1 : 2)) void k_walk_err_grad(
 #pragma unroll
         for (int t = 0; t < TS; ++t) Bk[t] = cadd(Bk[t], T2[t]);
         const int w_slot = P.nvg + e, z2_slot = P.nvg + P.ne + e * P.nvg;
-#if GRAPE_WALK_FDX_IN_ERR
         cd Mc[TS];  // M'_c (F_dx; every e-lane of an evaluation loads the same rows, the e = 0 lane stores)
         {
             const cd *Mcp = B.Mc + (sub * P.nchunks + c) * TS;
 #pragma unroll
             for (int t = 0; t < TS; ++t) Mc[t] = Mcp[t];
         }
-#endif
 #pragma unroll 1
         for (int jj = 0; jj < P.L; ++jj) {
             const int k = k0 + jj;
@@ -3153,20 +2864,14 @@ __global__ __launch_bounds__(kWalkBlock, (D >= 4 ? 1 : 2)) void k_walk_err_grad(
                         const cd a = z1[(size_t)(j * D + i) * lanes], bz = z2[(size_t)(j * D + i) * lanes];
                         s += Bk[i * D + j].re * a.re - Bk[i * D + j].im * a.im;
                         s += Mp[i * D + j].re * bz.re - Mp[i * D + j].im * bz.im;
-#if GRAPE_WALK_FDX_IN_ERR
                         sdx += Mc[i * D + j].re * a.re - Mc[i * D + j].im * a.im;
-#endif
                     }
                 }
-#if GRAPE_WALK_FDX_IN_ERR
                 if (e == 0) {  // F_dx[u, k] (sector part) = Re tr(M'_c Z1_u)
                     double *dx = act ? B.sec_part + ((((size_t)(w0 + w) * P.Nt) + k) * P.nvg + u) * nbe + be
                                      : reinterpret_cast<double *>(B.sink);
                     *dx = sdx;
                 }
-#else
-                (void)sdx;
-#endif
                 double *dst = act ? B.sec_part_err +
                                         (((((size_t)(w0 + w) * P.ne + e) * P.Nt + k) * P.nvg + u) * nbe + be)
                                   : reinterpret_cast<double *>(B.sink);
@@ -3219,15 +2924,6 @@ __global__ __launch_bounds__(kWalkBlock, (D >= 4 ? 1 : 2)) void k_walk_err_grad(
 // carries Q^ = D_{k+1}^dag Q (Q^ <- Om E~ Q^) or R~, and the chunk end maps back with D_next.
 // Six D x D products per step and error (k_walk_err_grad: two, plus 9 image reads; the image walk: two
 // per image), the live state three matrices (two waves per SIMD at D = 4).
-#ifndef GRAPE_WALK_WSUM_LAB_WAVES
-#define GRAPE_WALK_WSUM_LAB_WAVES 2
-#endif
-#ifndef GRAPE_WALK_ERR_LAB_WAVES
-#define GRAPE_WALK_ERR_LAB_WAVES 2
-#endif
-#ifndef GRAPE_WALK_ERR_LAB4_WAVES  // k_walk_err_lab<4>: four 4 x 4 complex matrices live (256 VGPRs) at the peak
-#define GRAPE_WALK_ERR_LAB4_WAVES 2
-#endif
 template <int D>
 constexpr int err_lab_waves() { return D >= 4 ? GRAPE_WALK_ERR_LAB4_WAVES : GRAPE_WALK_ERR_LAB_WAVES; }
 // the base table: lanes t < nsec (1 + 2 ne) compute exp(A0), exp(A0 + eps A_e0), exp(A0 + eps2 A_e0)
@@ -3250,7 +2946,7 @@ __global__ __launch_bounds__(kLabBaseMaxLanes) void k_gauge_err_base_fill(DevPro
         walk_build<D, 1>(P, as_constant(P.ops) + (size_t)w * P.sec_ops, X0, 1, none, A, e, ev);
         double mu0 = 0.0;
         cd *dst = out + (size_t)t * TS;
-        walk_expm<D, false, true, false>(A[0], scr + (size_t)t * 2 * TS, mu0, true, [&](int i, const cd (&x)[D]) {
+        walk_expm<D, false, false>(A[0], scr + (size_t)t * 2 * TS, mu0, true, [&](int i, const cd (&x)[D]) {
 #pragma unroll
             for (int j = 0; j < D; ++j) dst[j * D + i] = x[j];
         });
@@ -3271,9 +2967,6 @@ __global__ __launch_bounds__(kLabBaseMaxLanes) void k_gauge_err_base_fill(DevPro
 // barriers the scheduler interleaves the rows of a product and the loaded rows spill to VGPR lanes
 // (~700 v_writelane / v_readlane per step at D = 4: 39 % of the VALU instructions were not FP64); LDS
 // copies instead cost 190+ VGPRs of preloaded operands.
-#ifndef GRAPE_WALK_LAB_SEG
-#define GRAPE_WALK_LAB_SEG 1
-#endif
 struct LabBase {
     cptr<cd> g;  // the class's table
     int nb, ne, e;
@@ -3297,11 +2990,7 @@ __device__ __forceinline__ LabBase lab_step(LabBase b) {
     asm volatile("" : "+s"(b.g));
     return b;
 }
-__device__ __forceinline__ void lab_seg() {
-#if GRAPE_WALK_LAB_SEG
-    __builtin_amdgcn_sched_barrier(0);
-#endif
-}
+__device__ __forceinline__ void lab_seg() { __builtin_amdgcn_sched_barrier(0); }
 // row r of U through an opaque pointer tied to `dep` (an empty asm with a register input): neither the asm nor
 // the loads can move above the instruction that produced dep
 // the row's results pinned where the row ends (an empty asm that reads and rewrites them): instruction
@@ -3316,10 +3005,8 @@ __device__ __forceinline__ void lab_row(cptr<cd> U, int r, double dep, cd (&v)[D
     for (int j = 0; j < D; ++j) v[j] = cload(p, r * D + j);
 }
 // Row-wise consumption of a uniform matrix U: d_r = body(r, row r of U) (a result of the row), row r + 1 loaded
-// after row r - 1's result exists and consumed after a scheduling barrier: two rows live at most
-#ifndef GRAPE_WALK_LAB_PREFETCH  // row r + 1's loads issued with row r's FMAs
-#define GRAPE_WALK_LAB_PREFETCH 1
-#endif
+// after row r - 1's result exists (its loads issued with row r's FMAs) and consumed after a scheduling barrier:
+// two rows live at most
 template <int D, class Body>
 __device__ __forceinline__ void lab_rows(cptr<cd> U, double dep0, Body &&body) {
     cd cur[D], nxt[D];
@@ -3327,11 +3014,10 @@ __device__ __forceinline__ void lab_rows(cptr<cd> U, double dep0, Body &&body) {
     double dprev = dep0;
 #pragma unroll
     for (int r = 0; r < D; ++r) {
-        if (GRAPE_WALK_LAB_PREFETCH && r + 1 < D) lab_row<D>(U, r + 1, dprev, nxt);
+        if (r + 1 < D) lab_row<D>(U, r + 1, dprev, nxt);
         const double d = body(r, cur);
         lab_seg();
         if (r + 1 < D) {
-            if (!GRAPE_WALK_LAB_PREFETCH) lab_row<D>(U, r + 1, d, nxt);
 #pragma unroll
             for (int j = 0; j < D; ++j) cur[j] = nxt[j];
         }
@@ -3441,14 +3127,13 @@ __global__ __launch_bounds__(kWalkBlock, GRAPE_WALK_WSUM_LAB_WAVES) void k_walk_
     const WalkLane L = walk_lane<NS>(P, B, vb);
     const int ns = P.nsec > 1 ? P.nsec : 1, e = blockIdx.z;
     const bool tc = e == P.ne;  // (workgroup-uniform)
-    const double *xt = B.xT + (size_t)L.be * (kWalkXRow ? P.nx : 1);
-    const int xs = kWalkXRow ? 1 : L.nbe;
+    const double *xt = B.xT + (size_t)L.be * P.nx;  // this evaluation's row of x (B.xT = B.x)
     const LabBase lb = lab_base(P, e);
     GaugeN<D> gn[NS];
 #pragma unroll
     for (int w = 0; w < NS; ++w) gn[w] = gauge_charges<D>(P, L.w0 + w);
     const int k0 = L.c * P.L;
-    double xk = walk_load_x(1, xt + (size_t)min(k0, P.Nt - 1) * xs, xs).v0;
+    double xk = walk_load_x(1, xt + (size_t)min(k0, P.Nt - 1)).v0;
     // Q^ = D_{k0}^dag (Q = I at the chunk start), R~ = 0
     cd S[NS][D][D];
     {
@@ -3466,7 +3151,7 @@ __global__ __launch_bounds__(kWalkBlock, GRAPE_WALK_WSUM_LAB_WAVES) void k_walk_
     double xnext = xk;
     auto step = [&](int jj) {
         const int k = min(k0 + jj, P.Nt - 1);
-        xnext = walk_load_x(1, xt + (size_t)min(k + 1, P.Nt - 1) * xs, xs).v0;
+        xnext = walk_load_x(1, xt + (size_t)min(k + 1, P.Nt - 1)).v0;
         const cd om = gauge_cis(P.gauge_a * xk - P.gauge_a * xnext);  // Om = D_{k+1}^dag D_k
         xk = xnext;
         const LabBase lbs = lab_step(lb);
@@ -3534,14 +3219,13 @@ __global__ __launch_bounds__(kWalkBlock, err_lab_waves<D>()) void k_walk_err_lab
     const WalkLane L = walk_lane<NS>(P, B, vb);
     const int ns = P.nsec > 1 ? P.nsec : 1, e = blockIdx.z;
     const bool fdx = e == P.ne;  // (workgroup-uniform)
-    const double *xt = B.xT + (size_t)L.be * (kWalkXRow ? P.nx : 1);
-    const int xs = kWalkXRow ? 1 : L.nbe;
+    const double *xt = B.xT + (size_t)L.be * P.nx;  // this evaluation's row of x (B.xT = B.x)
     const LabBase lb = lab_base(P, e);
     GaugeN<D> gn[NS];
 #pragma unroll
     for (int w = 0; w < NS; ++w) gn[w] = gauge_charges<D>(P, L.w0 + w);
     const int k0 = L.c * P.L;
-    double xk = walk_load_x(1, xt + (size_t)min(k0, P.Nt - 1) * xs, xs).v0;
+    double xk = walk_load_x(1, xt + (size_t)min(k0, P.Nt - 1)).v0;
     cd X[NS][D][D], Lm[NS][D][D];
 #pragma unroll
     for (int w = 0; w < NS; ++w) {
@@ -3592,7 +3276,7 @@ __global__ __launch_bounds__(kWalkBlock, err_lab_waves<D>()) void k_walk_err_lab
         for (int jj = 0; jj < P.L; ++jj) {
             const int k = min(k0 + jj, P.Nt - 1);
             const bool act = L.ok && k0 + jj < P.Nt;
-            const double xn = walk_load_x(1, xt + (size_t)min(k + 1, P.Nt - 1) * xs, xs).v0;
+            const double xn = walk_load_x(1, xt + (size_t)min(k + 1, P.Nt - 1)).v0;
             const cd q1 = cis_m1(P.gauge_a * ((xk + P.eps) - xk));
             const cd om = gauge_cis(P.gauge_a * xk - P.gauge_a * xn);
             xk = xn;
@@ -3618,7 +3302,7 @@ __global__ __launch_bounds__(kWalkBlock, err_lab_waves<D>()) void k_walk_err_lab
     for (int jj = 0; jj < P.L; ++jj) {
         const int k = min(k0 + jj, P.Nt - 1);
         const bool act = L.ok && k0 + jj < P.Nt;
-        const double xn = walk_load_x(1, xt + (size_t)min(k + 1, P.Nt - 1) * xs, xs).v0;
+        const double xn = walk_load_x(1, xt + (size_t)min(k + 1, P.Nt - 1)).v0;
         const cd q1 = cis_m1(P.gauge_a * ((xk + P.eps) - xk)), q2 = cis_m1(P.gauge_a * ((xk + P.eps2) - xk));
         const cd om = gauge_cis(P.gauge_a * xk - P.gauge_a * xn);
         xk = xn;

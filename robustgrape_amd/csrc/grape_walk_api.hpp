@@ -12,19 +12,9 @@ constexpr int kGaugeMaxE = 8;  // error sources of a phase-covariant image walk 
 constexpr int kWalkBlockA = 128;  // lanes per workgroup (grape_walk.hpp kWalkBlock)
 // walk classes of at least this many levels hand the forward walk's propagators to the gradient walk
 // (B.Ew) instead of recomputing them (the engine's P.walk_store_e and the launchers agree on it)
-#ifndef GRAPE_WALK_STORE_MIN_D
-#define GRAPE_WALK_STORE_MIN_D 4
-#endif
-constexpr int kWalkStoreMinD = GRAPE_WALK_STORE_MIN_D;
-// GRAPE_WALK_XROW: the walks read the controls row-major from x itself (B.xT = x, stride 1 per value,
-// nx per evaluation) instead of a transposed copy, and the engine skips k_transpose_x.  Each lane
-// streams its own row: 8 steps per 64-B line, reused from the vector cache.  Round 4 (per-class
-// walks) measured it neutral; with the merged walks it wins: C2 36.8 -> 38.4 M evals/s (fwd 0.269 ->
-// 0.222, grad 0.470 -> 0.481 ms per pass, no transpose; profiles/r05/ab_xrow)
-#ifndef GRAPE_WALK_XROW
-#define GRAPE_WALK_XROW 1
-#endif
-constexpr bool kWalkXRow = GRAPE_WALK_XROW;
+constexpr int kWalkStoreMinD = 4;
+// The walks read the controls row-major from x itself (B.xT = B.x: stride 1 per value, nx per evaluation; no
+// transposed copy).  Each lane streams its own row: 8 steps per 64-B line, reused from the vector cache.
 // error sources on a phase-covariant class (round 6): the lab-frame walks k_walk_wsum_lab / k_walk_err_lab
 // (grape_walk.hpp; the engine's P.gauge_lab), no images.  0: the image walk and its back end (A/B)
 #ifndef GRAPE_WALK_ERR_LAB
@@ -56,10 +46,9 @@ hipError_t launch_pair(int stage, const grape::DevProblem &P0, const grape::DevB
 // both classes of an (evaluation, chunk) (k_walk_fwd_m / k_walk_grad_m); the gradient stage writes
 // one F_dx part, class 0's + class 1's (a_first: class A is the plan's class 0), into class A's
 // sec_part.  Stage 0: k_walk_fwd_m (chunk totals, lane-minor), stage 2: k_scan_seq (carries and U
-// from them), stage 1: k_walk_grad_m.  merged_ok tells whether the classes fit.
+// from them), stage 1: k_walk_grad_m, which writes the F_dx rows itself (no k_sec_reduce for such passes).
+// merged_ok tells whether the classes fit.
 bool merged_ok(const grape::DevProblem &PA, const grape::DevProblem &PB);
-// 1: the merged gradient walk writes F_dx rows itself (no k_sec_reduce for such passes)
-bool merged_writes_fdx();
 // 1: the merged gradient walk carries one summed state for a twin class's two sectors (GRAPE_WALK_TWIN_SUM)
 bool merged_twin_sum();
 // E~ of the class's nsec sectors into out [nsec][D][D] (DevProblem::gauge_Et; scr: 2 D^2 complex per sector)
@@ -80,8 +69,6 @@ bool wide_ok(const grape::DevProblem &PA, const grape::DevProblem &PB);
 hipError_t launch_merged_wide(int stage, const grape::DevProblem &PA, const grape::DevBatch &BA, const grape::DevProblem &PB,
                               const grape::DevBatch &BB, int a_first, hipStream_t st);
 // F_dx parts the class's gradient stage writes per evaluation: its sectors, or (k_walk_grad with several
-// sectors per lane, no error sources) one pre-summed part per lane row (grape_walk.hpp kWalkPresum)
+// sectors per lane, no error sources) one pre-summed part per lane row (grape_walk.hpp walk_grad_body)
 int grad_parts(const grape::DevProblem &P);
-// the walks' controls: x [nb][nx] -> xT [nx][nb] (B.xT), once per launch for every walk class
-hipError_t transpose_x(const double *x, double *xT, int nb, int nx, hipStream_t st);
 }  // namespace grape_walk

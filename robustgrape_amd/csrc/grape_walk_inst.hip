@@ -25,10 +25,8 @@ void launch_ns(int stage, const grape::DevProblem &P, const grape::DevBatch &B, 
         if (stage == 0) {
             if (P.gauge) hipLaunchKernelGGL((grape::k_walk_img_gauge<D, NS>), grid, blk, 0, st, P, B);
             else hipLaunchKernelGGL((grape::k_walk_img<D, NS>), grid, blk, 0, st, P, B);
-        } else if (stage == 1) {  // F_dx traces of Z1 and the chunk sums of W (k_err_scan's Phase A)
-            // (the 2-level image walk summed W itself: WalkCfg::IMG_WSUM)
-            if (!(grape::WalkCfg<D, NS>::IMG_WSUM && P.ne <= grape::kWsumMaxE))
-                hipLaunchKernelGGL((grape::k_walk_img_sum<D, NS>), grid, blk, 0, st, P, B);
+        } else if (stage == 1) {  // the chunk sums of W (k_err_scan's Phase A)
+            hipLaunchKernelGGL((grape::k_walk_img_sum<D, NS>), grid, blk, 0, st, P, B);
         } else {  // the F_d2err_dx walks, one lane per (chunk, evaluation, error)
             const dim3 grid_e((unsigned)((lanes * P.ne + grape::kWalkBlock - 1) / grape::kWalkBlock), (unsigned)(ns / NS));
             hipLaunchKernelGGL((grape::k_walk_err_grad<D, NS>), grid_e, blk, 0, st, P, B);
@@ -79,10 +77,6 @@ hipError_t launch(int stage, const grape::DevProblem &P, const grape::DevBatch &
     const int ns = P.nsec > 1 ? P.nsec : 1;
     if ((long)(B.nb / ns) * P.nchunks <= 0) return hipSuccess;
     if constexpr (D == 2) {  // (the Rydberg two-level classes; a three-level class takes one sector per lane)
-        if (GRAPE_WALK_IMG2_NS1 && P.ne > 0) {
-            launch_ns<D, 1>(stage, P, B, st);
-            return hipGetLastError();
-        }
         if (ns == 2) {
             launch_ns<D, 2>(stage, P, B, st);
             return hipGetLastError();
@@ -98,7 +92,7 @@ hipError_t launch(int stage, const grape::DevProblem &P, const grape::DevBatch &
 
 int grad_parts(const grape::DevProblem &P) {
     const int ns = P.nsec > 1 ? P.nsec : 1;
-    if (!grape::kWalkPresum || P.ne > 0 || P.D != 2) return ns;
+    if (P.ne > 0 || P.D != 2) return ns;
     if (ns == 2 || ns == 3) return 1;  // launch<2>: both (all three) sectors in one lane
     return ns;
 }
@@ -154,7 +148,6 @@ bool merged_ok(const grape::DevProblem &PA, const grape::DevProblem &PB) {
            PA.nchunks == PB.nchunks && PA.np == 1 && PA.na <= 1 && !PA.xadd_dep && !PB.xadd_dep &&
            PA.nvg == 1 && PB.nvg == 1 && PA.ne == 0 && PB.ne == 0;
 }
-bool merged_writes_fdx() { return GRAPE_WALK_MERGED_FDX != 0; }
 bool merged_twin_sum() { return GRAPE_WALK_TWIN_SUM != 0; }
 hipError_t fill_gauge_base(const grape::DevProblem &P, int nsec, grape::cd *scr, grape::cd *out, hipStream_t st) {
     if (nsec < 1 || nsec > 64) return hipErrorInvalidValue;
@@ -209,10 +202,8 @@ hipError_t launch_merged(int stage, const grape::DevProblem &PA, const grape::De
     return hipGetLastError();
 }
 bool wide_ok(const grape::DevProblem &PA, const grape::DevProblem &PB) {
-    // rank-one plans with E~ tables; the lanes read x rows in place (GRAPE_WALK_XROW) and the gradient walk
-    // writes F_dx itself; N_t <= 4096: the recompute drift of psi is checked to there
-    return merged_ok(PA, PB) && PA.rank1 && PB.rank1 && PA.gauge_Et && PB.gauge_Et && grape::kWalkXRow &&
-           GRAPE_WALK_MERGED_FDX != 0 && PA.Nt <= kWideMaxNt;
+    // rank-one plans with E~ tables; N_t <= 4096: the recompute drift of psi is checked to there
+    return merged_ok(PA, PB) && PA.rank1 && PB.rank1 && PA.gauge_Et && PB.gauge_Et && PA.Nt <= kWideMaxNt;
 }
 hipError_t launch_merged_wide(int stage, const grape::DevProblem &PA, const grape::DevBatch &BA, const grape::DevProblem &PB,
                               const grape::DevBatch &BB, int a_first, hipStream_t st) {
@@ -231,28 +222,6 @@ hipError_t launch_merged_wide(int stage, const grape::DevProblem &PA, const grap
         lad ? go(I3{}, std::true_type{}, std::true_type{}) : go(I3{}, std::true_type{}, std::false_type{});
     else
         lad ? go(I3{}, std::false_type{}, std::true_type{}) : go(I3{}, std::false_type{}, std::false_type{});
-    return hipGetLastError();
-}
-
-// x [nb][nx] -> xT [nx][nb] through a 32 x 32 LDS tile (both sides coalesced)
-__global__ __launch_bounds__(256) void k_transpose_x(const double *x, double *xT, int nb, int nx) {
-    __shared__ double t[32][33];
-    const int b0 = blockIdx.x * 32, q0 = blockIdx.y * 32, tx = threadIdx.x % 32, ty = threadIdx.x / 32;
-    for (int i = ty; i < 32; i += 8) {
-        const int b = b0 + i, q = q0 + tx;
-        if (b < nb && q < nx) t[i][tx] = x[(size_t)b * nx + q];
-    }
-    __syncthreads();
-    for (int i = ty; i < 32; i += 8) {
-        const int q = q0 + i, b = b0 + tx;
-        if (b < nb && q < nx) xT[(size_t)q * nb + b] = t[tx][i];
-    }
-}
-
-hipError_t transpose_x(const double *x, double *xT, int nb, int nx, hipStream_t st) {
-    if (nb <= 0) return hipSuccess;
-    hipLaunchKernelGGL(k_transpose_x, dim3((unsigned)((nb + 31) / 32), (unsigned)((nx + 31) / 32)), dim3(256), 0, st, x,
-                       xT, nb, nx);
     return hipGetLastError();
 }
 

@@ -53,6 +53,23 @@ def test_library_build_id_is_the_source_hash(tmp_path):
     assert build.source_id() == _capi.build_id() and not build.needs_build()
 
 
+def test_every_included_file_is_hashed():
+    """source_id() covers what the compiler reads: every `#include "..."` of every file in build.DEPS
+    names a file under csrc/ or include/ that is itself in DEPS (an edit to a header that is not would
+    leave the build id unchanged and the stale library accepted)."""
+    from robustgrape_amd import build
+    deps = {os.path.realpath(d) for d in build.DEPS}
+    dirs = [build.CSRC, os.path.join(ROOT, "include")]
+    n = 0
+    for d in build.DEPS:
+        for inc in re.findall(r'^\s*#\s*include\s+"([^"]+)"', open(d).read(), re.M):
+            found = [os.path.join(base, inc) for base in dirs if os.path.isfile(os.path.join(base, inc))]
+            assert found, f"{os.path.basename(d)} includes {inc}: not under csrc/ or include/"
+            assert os.path.realpath(found[0]) in deps, f"{os.path.basename(d)} includes {inc}: not in build.DEPS"
+            n += 1
+    assert n > 0
+
+
 def test_descriptor_packing_roundtrip():
     """The ctypes descriptor reproduces the operator basis (column-major, interleaved)."""
     from robustgrape_amd.operators import DescriptorBuffers
