@@ -1904,7 +1904,6 @@ static int enqueue_wide(grape_plan *p, int nb, const double *d_x, double *d_F, d
         Pw[i].L = Pw[i].Nt;
         Bw[i].nb = nb * Pw[i].nsec;
         Bw[i].x = d_x;
-        Bw[i].xT = d_x;
         Bw[i].F = d_F;
         Bw[i].Fdx = d_Fdx;
         Bw[i].Ub = sb.Tc;
@@ -1989,7 +1988,6 @@ static int enqueue(grape_plan *p, int nb, const double *d_x, double *d_F, double
             B.Tc = sb.Tc;  // chunk walks (null otherwise)
             B.wscr = sb.wscr;
             B.Ew = sb.Ew;
-            B.xT = d_x;  // the walks read x rows in place
             sp.part[cl] = sb.part;
             sp.nsec[cl] = p->Ps[cl].walk ? grape_walk::grad_parts(p->Ps[cl]) : p->Ps[cl].nsec;
             if (p->merged && cl != p->merge_pa) sp.nsec[cl] = 0;  // (the merged walk's one part is class A's)

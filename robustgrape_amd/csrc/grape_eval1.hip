@@ -16,17 +16,22 @@
 //              (FidelityCalculations.jl:47-76, the diagonal head of grape_projector.hip)
 //   phase D    lane c: X = S_{c-1} M S_{c-1}^dag, then per step Y = X E_k^dag,
 //              F_dx[k] = Re tr(Y (E'_k - E_k)) / eps with E' - E = E o f from the level phases,
-//              X <- E_k Y (grape_walk.hpp walk_grad_body's GAUGE step)
+//              X <- E_k Y (grape_walk_chunk.hpp walk_grad_body's GAUGE step)
 //   phase E    F_dx[k] = class 0's part + class 1's part, coalesced stores
 //
 // Same quantities and the same per-step arithmetic as the chunk walks; the chain products are
 // associated differently (a scan over 256 chunks instead of the pair path's walk + scan
 // geometry), so results agree with the pair path to rounding, not bit for bit.
+//
+// Of the walk headers this unit takes two pieces: grape_walk_core.hpp (the term builder and the column
+// exponential: walk_build, walk_expm, SM, WalkX, as_constant) and grape_walk_gauge.hpp (GaugeN, gauge_cis,
+// cis_m1, gauge_phases, gauge_sandwich and the difference weights).  It launches none of the walk kernels.
 #include <bitset>
 #include <mutex>
 
 #include "grape_eval1_api.hpp"
-#include "grape_walk.hpp"
+#include "grape_walk_core.hpp"
+#include "grape_walk_gauge.hpp"
 
 namespace grape_eval1 {
 using namespace grape;

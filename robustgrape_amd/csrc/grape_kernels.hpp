@@ -154,7 +154,6 @@ struct DevBatch {
     cd *gp_scr;             // general projector: head scratch (grape_projector_api.hpp)
     double *sec_part;       // sectors: [nb][Nt][nvg] per-sector F_dx terms (k_sec_reduce sums them), else null;
                             // chunk walks: [nsec][Nt][nvg][nb / nsec], the evaluation fastest (coalesced)
-    const double *xT;       // chunk walks: always equal to x (they read x rows in place; the field keeps the layout)
     const cd *Msec;         // sectors: [nb][D][D] the sector blocks of M = G U (the sector head)
     // sectors with error sources
     double *sec_part_err;   // [nb][ne][Nt][nvg] per-sector F_d2err_dx terms (k_sec_reduce_err sums them)

@@ -13,8 +13,8 @@ constexpr int kWalkBlockA = 128;  // lanes per workgroup (grape_walk.hpp kWalkBl
 // walk classes of at least this many levels hand the forward walk's propagators to the gradient walk
 // (B.Ew) instead of recomputing them (the engine's P.walk_store_e and the launchers agree on it)
 constexpr int kWalkStoreMinD = 4;
-// The walks read the controls row-major from x itself (B.xT = B.x: stride 1 per value, nx per evaluation; no
-// transposed copy).  Each lane streams its own row: 8 steps per 64-B line, reused from the vector cache.
+// The walks read the controls row-major from x itself (stride 1 per value, nx per evaluation; no transposed
+// copy).  Each lane streams its own row: 8 steps per 64-B line, reused from the vector cache.
 // error sources on a phase-covariant class (round 6): the lab-frame walks k_walk_wsum_lab / k_walk_err_lab
 // (grape_walk.hpp; the engine's P.gauge_lab), no images.  0: the image walk and its back end (A/B)
 #ifndef GRAPE_WALK_ERR_LAB

@@ -1,5 +1,7 @@
-// grape_walk_inst.hip -- the chunk-walk kernels (grape_walk.hpp) for D = 2 .. kWalkMaxD and their
-// launchers; built with -mllvm -disable-machine-licm (robustgrape_amd/build.py).
+// grape_walk_inst.hip -- the chunk-walk kernels (grape_walk.hpp and its pieces) for D = 2 .. kWalkMaxD and
+// their launchers; built with -mllvm -disable-machine-licm (robustgrape_amd/build.py).  ONE translation unit
+// for every family, instantiated in the order below: the merged matrix gradient walk's code generation
+// depends on what else the unit holds.
 #include <type_traits>
 
 #include "grape_walk.hpp"
@@ -170,6 +172,17 @@ hipError_t fill_gauge_err_base(const grape::DevProblem &P, int nsec, grape::cd *
     }
     return hipGetLastError();
 }
+// The merged launchers' kernel variant, go(DA, TW, LAD): class A of 3 levels (merged_ok), twin sectors in
+// class B, ladder charges in both classes (DevProblem::gauge_ladder): compile-time charge differences
+template <class Go>
+void merged_variant(const grape::DevProblem &PA, const grape::DevProblem &PB, Go &&go) {
+    using I3 = std::integral_constant<int, 3>;
+    const bool lad = PA.gauge_ladder && PB.gauge_ladder;
+    if (PB.twin)
+        lad ? go(I3{}, std::true_type{}, std::true_type{}) : go(I3{}, std::true_type{}, std::false_type{});
+    else
+        lad ? go(I3{}, std::false_type{}, std::true_type{}) : go(I3{}, std::false_type{}, std::false_type{});
+}
 hipError_t launch_merged(int stage, const grape::DevProblem &PA, const grape::DevBatch &BA, const grape::DevProblem &PB,
                          const grape::DevBatch &BB, int a_first, hipStream_t st) {
     if (!merged_ok(PA, PB)) return hipErrorInvalidValue;
@@ -192,13 +205,7 @@ hipError_t launch_merged(int stage, const grape::DevProblem &PA, const grape::De
             hipLaunchKernelGGL((grape::k_walk_grad_m<DA, TW, LAD, false>), grid, blk, 0, st, PA, BA, PB, BB, a_first);
         }
     };
-    using I3 = std::integral_constant<int, 3>;
-    // ladder charges in both classes (DevProblem::gauge_ladder): compile-time charge differences
-    const bool lad = PA.gauge_ladder && PB.gauge_ladder;
-    if (PB.twin)
-        lad ? go(I3{}, std::true_type{}, std::true_type{}) : go(I3{}, std::true_type{}, std::false_type{});
-    else
-        lad ? go(I3{}, std::false_type{}, std::true_type{}) : go(I3{}, std::false_type{}, std::false_type{});
+    merged_variant(PA, PB, go);
     return hipGetLastError();
 }
 bool wide_ok(const grape::DevProblem &PA, const grape::DevProblem &PB) {
@@ -216,12 +223,7 @@ hipError_t launch_merged_wide(int stage, const grape::DevProblem &PA, const grap
         if (stage == 0) hipLaunchKernelGGL((grape::k_walk_fwd_m<DA, TW, LAD, true>), grid, blk, 0, st, PA, BA, PB, BB);
         else hipLaunchKernelGGL((grape::k_walk_grad_m<DA, TW, LAD, true, true>), grid, blk, 0, st, PA, BA, PB, BB, a_first);
     };
-    using I3 = std::integral_constant<int, 3>;
-    const bool lad = PA.gauge_ladder && PB.gauge_ladder;
-    if (PB.twin)
-        lad ? go(I3{}, std::true_type{}, std::true_type{}) : go(I3{}, std::true_type{}, std::false_type{});
-    else
-        lad ? go(I3{}, std::false_type{}, std::true_type{}) : go(I3{}, std::false_type{}, std::false_type{});
+    merged_variant(PA, PB, go);
     return hipGetLastError();
 }
 

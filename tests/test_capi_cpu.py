@@ -70,6 +70,28 @@ def test_every_included_file_is_hashed():
     assert n > 0
 
 
+def _walk_pieces():
+    """The piece headers of the walks: what the umbrella csrc/grape_walk.hpp includes."""
+    src = open(os.path.join(ROOT, "robustgrape_amd", "csrc", "grape_walk.hpp")).read()
+    return re.findall(r'^#include "(grape_walk_\w+\.hpp)"', src, re.M)
+
+
+def test_walk_umbrella_lists_its_pieces():
+    assert len(_walk_pieces()) >= 6 and len(set(_walk_pieces())) == len(_walk_pieces())
+
+
+@pytest.mark.parametrize("piece", _walk_pieces())
+def test_walk_piece_compiles_on_its_own(piece, tmp_path):
+    """Every piece of grape_walk.hpp includes what it uses: a file that holds nothing but its #include
+    passes the compiler's front end with the library's flags (host and device pass, no code generation)."""
+    import subprocess
+    from robustgrape_amd import build
+    unit = tmp_path / "piece.hip"
+    unit.write_text(f'#include "{piece}"\n')
+    r = subprocess.run([build.HIPCC] + build.FLAGS + ["-fsyntax-only", str(unit)], capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr[-4000:]
+
+
 def test_descriptor_packing_roundtrip():
     """The ctypes descriptor reproduces the operator basis (column-major, interleaved)."""
     from robustgrape_amd.operators import DescriptorBuffers

@@ -30,13 +30,13 @@ def _need_gpu():
         pytest.skip("no GPU")
 
 
-def _plan(fp, max_batch, options=0, nparam=1):
+def _plan(fp, max_batch, options=0, nparam=1, scan_waves=0):
     from robustgrape_amd.engine import GrapePlan
-    return GrapePlan(fp, nparam=nparam, device=0, max_batch=max_batch, options=options)
+    return GrapePlan(fp, nparam=nparam, device=0, max_batch=max_batch, options=options, scan_waves=scan_waves)
 
 
-def _run(fp, X, options=0, nparam=1, expect_walk=None):
-    pl = _plan(fp, len(X), options, nparam)
+def _run(fp, X, options=0, nparam=1, expect_walk=None, scan_waves=0):
+    pl = _plan(fp, len(X), options, nparam, scan_waves)
     try:
         pl.set_profiling(True)
         out = pl.fidelity_grad(X)
@@ -114,6 +114,31 @@ def test_image_walk_matches_oracle_and_stored_path(name, mk, layout):
         tier = P.fd_tier(f, X[b])
         _check_all(f"imgwalk_vs_oracle_{name}_{b}", out, b, O.calculate_fidelity_and_derivatives(fo, X[b]), tier, nt,
                    exact_rows(f, X[b]))
+
+
+@pytest.mark.parametrize("nt,scan_waves", [(33, 0), (33, 1), (35, 1)])
+def test_per_step_image_walk_ragged_last_chunk(nt, scan_waves):
+    """The image walk proper (GRAPE_OPT_NO_GAUGE: k_walk_img, k_walk_img_sum, k_walk_err_grad; by default
+    these phase-covariant classes take the lab-frame walks) where the last chunk runs past N_t, so
+    k_walk_img_sum's sums must leave out steps that do not exist.  Chunking (decide_class): five
+    evaluations take the 8-wave scans, 128 / 256 chunks, hence one step per chunk at N_t = 33 -- nothing
+    ragged; one-wave scans (scan_waves = 1, the throughput chunking: at most 16 chunks at 4 levels, 32 at
+    2) give at N_t = 33 11 chunks of 3 (exact) and 17 of 2 (34 > 33), at N_t = 35 12 of 3 and 18 of 2
+    (36 > 35 in both classes).  Against the stored-intermediate path and the oracle."""
+    from oracle import grape_oracle as O
+    from robustgrape_amd.operators import OPT_NO_GAUGE, OPT_NO_WALK
+    f, fo = P.full9_problem(nt, nerr=2), P.full9_problem(nt, nerr=2, device=False)
+    X = np.stack([P.random_x(nt, 900 + s) for s in range(5)])
+    out, sec = _run(f, X, OPT_NO_GAUGE, expect_walk=True, scan_waves=scan_waves)
+    ref, _ = _run(f, X, OPT_NO_WALK, expect_walk=False)
+    assert sec == ((4, 1), (2, 2))
+    name = f"nt{nt}_w{scan_waves}"
+    for b in range(len(X)):
+        _check_all(f"imgwalk_ragged_vs_stored_{name}_{b}", out, b, tuple(r[b] for r in ref), P.fd_tier(f, X[b]), nt,
+                   exact_rows(f, X[b]))
+    for b in (0, 4):
+        _check_all(f"imgwalk_ragged_vs_oracle_{name}_{b}", out, b, O.calculate_fidelity_and_derivatives(fo, X[b]),
+                   P.fd_tier(f, X[b]), nt, exact_rows(f, X[b]))
 
 
 def test_image_walk_bench_size_against_oracle():
