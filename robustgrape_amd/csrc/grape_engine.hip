@@ -566,7 +566,12 @@ static int upload_projector(grape_plan *p, const ProjectorSetup &ps, DevProblem 
 // Sectors: connected components of the union sparsity pattern of every operator H0 uses
 // (the levels an evolution can ever couple).  A single level with a zero diagonal in every
 // operator never evolves (its propagator is 1 and it carries no gradient): it is "fixed" and
-// only enters the head's U.  The others are packed first-fit-decreasing into sectors of
+// only enters the head's U.  A single level with a diagonal entry evolves by a phase of its own; when
+// it is idle (idle_levels: no projector weight, no target entry beside its diagonal) that phase reaches
+// neither F nor any derivative -- every term of the heads carries P0 or its pattern on both sides of
+// K = U0^dag U, block diagonal there -- and the level is left out altogether (the dark state
+// (|1r> - |r1>) / sqrt 2 of the detuned d = 9 Rydberg model: as a third, padded 2-level sector it kept
+// the plan off the pair, merged and one-workgroup kernels).  The others are packed first-fit-decreasing into sectors of
 // S = max(2, largest component) slots -- one class -- or, when that costs at least a quarter
 // less work (sum of nsec S^3), into two classes: the components above a size cut in sectors of
 // their largest size, the rest in sectors of theirs (d = 9 Rydberg: one sector of 4 and two of
@@ -603,7 +608,7 @@ static SectorClass pack_sectors(const std::vector<std::vector<int>> &comps) {  /
     return sc;
 }
 static long sector_cost(const SectorClass &c) { return (long)c.nsec * c.S * c.S * c.S; }
-static SectorSetup find_sectors(const grape_desc *desc, bool tables) {
+static SectorSetup find_sectors(const grape_desc *desc, bool tables, const std::vector<char> *idle = nullptr) {
     SectorSetup ss;
     const int D = desc->ndim;
     if (tables || D > GRAPE_MAX_SMALL_DIM || (desc->reserved[1] & GRAPE_OPT_NO_SECTORS)) return ss;
@@ -642,7 +647,8 @@ static SectorSetup find_sectors(const grape_desc *desc, bool tables) {
     const size_t ncomp = comps.size();
     comps.erase(std::remove_if(comps.begin(), comps.end(),
                                [&](const std::vector<int> &c) {
-                                   if (c.size() != 1 || diag[c[0]]) return false;
+                                   if (c.size() != 1) return false;
+                                   if (diag[c[0]]) return idle && (*idle)[c[0]] != 0;  // (left out: not fixed)
                                    fixed.push_back(c[0]);
                                    return true;
                                }),
@@ -669,6 +675,24 @@ static SectorSetup find_sectors(const grape_desc *desc, bool tables) {
     ss.cls = best;
     ss.fixed = fixed;
     return ss;
+}
+
+// Levels that cannot reach F or a derivative of it when no operator couples them to another level (find_sectors):
+// diagonal projector (in the sector path's basis) without weight on the level, and every target operator free of
+// entries beside the diagonal in the level's row and column.
+static std::vector<char> idle_levels(const grape_desc *desc, const grape_desc &sdesc, const ProjectorSetup &sps) {
+    const int D = desc->ndim;
+    std::vector<char> idle(D, 0);
+    if (sps.general || !desc->target_terms) return idle;
+    for (int g = 0; g < D; ++g) idle[g] = sps.W[g] == 0.0;
+    for (int k = 0; k < desc->n_target_terms; ++k) {
+        const double *op = sdesc.ops + 2 * (size_t)desc->target_terms[k].op * D * D;
+        for (int i = 0; i < D; ++i)
+            for (int j = 0; j < D; ++j)
+                if (i != j && (op[2 * (i + (size_t)j * D)] != 0.0 || op[2 * (i + (size_t)j * D) + 1] != 0.0))
+                    idle[i] = idle[j] = 0;
+    }
+    return idle;
 }
 
 // Phase covariance of a sector class (grape_walk.hpp GAUGE): does every sector block obey
@@ -1178,7 +1202,10 @@ static int setup_problem(PlanBuild &b) {
     // splits the sectors further; the whole-matrix problem P keeps the caller's basis
     if (!b.rt.general_h0 && !b.rt.tables) b.sym = symmetry_setup(desc);
     b.sdesc = b.sym.on ? b.sym.view(desc) : *desc;
-    if (!b.rt.general_h0) b.ss = find_sectors(&b.sdesc, b.rt.tables);
+    if (!b.rt.general_h0) {
+        const std::vector<char> idle = b.rt.tables ? std::vector<char>() : idle_levels(desc, b.sdesc, b.sps());
+        b.ss = find_sectors(&b.sdesc, b.rt.tables, b.rt.tables ? nullptr : &idle);
+    }
     p->symmetry = b.sym.on;
     return GRAPE_OK;
 }

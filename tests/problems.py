@@ -17,15 +17,16 @@ W_FULLBLK = np.diag([1.0, 1.0, 1.0, 1.0, 0.0, 0.0, 0.0])  # runtests.jl:492
 W_FULL9 = np.diag([1.0, 1.0, 1.0, 1.0, 0.0, 0.0, 0.0, 0.0, 0.0])
 
 
-def sym_problem(ntimes, t0=T0_TEST, errors=(), device=True):
-    """d=5 symmetric blockaded CZ (runtests.jl:57-75); errors subset of {'amp','freq'}."""
+def sym_problem(ntimes, t0=T0_TEST, errors=(), device=True, delta=0.0):
+    """d=5 symmetric blockaded CZ (runtests.jl:57-75); errors subset of {'amp','freq'}; delta: H0's
+    detuning (the reference's tests leave it 0)."""
     if device:
-        H0 = R.rydberg_symmetric_blockaded_operator_basis()
+        H0 = R.rydberg_symmetric_blockaded_operator_basis(delta=delta)
         errs = [ErrorSource(R.symmetric_amplitude_error() if e == "amp" else R.symmetric_frequency_error())
                 for e in errors]
         target = R.cz_symmetric_target()
     else:
-        H0 = lambda t, p, xa: R.rydberg_hamiltonian_symmetric_blockaded(p[0], 0, 0)
+        H0 = lambda t, p, xa: R.rydberg_hamiltonian_symmetric_blockaded(p[0], 0, delta)
         amp = lambda t, p, xa, e: (R.rydberg_hamiltonian_symmetric_blockaded(p[0], e, 0)
                                    - R.rydberg_hamiltonian_symmetric_blockaded(p[0], 0, 0))
         frq = lambda t, p, xa, e: (R.rydberg_hamiltonian_symmetric_blockaded(p[0], 0, e)
@@ -90,6 +91,103 @@ def full9_problem(ntimes=512, t0=T0_TO, nerr=0, device=True, B=10.0):
     up = UnitaryRobustGRAPEProblem(t0=t0, ntimes=ntimes, ndim=9, H0=H0, nb_additional_param=1,
                                    error_sources=errs)
     return FidelityRobustGRAPEProblem(up, W_FULL9, target)
+
+
+def full9_family(ntimes, t0=T0_TO, om=1.0, om01=None, delta=0.0, d0r=0.0, B=10.0, a=1.0, b=0.0, device=True):
+    """The d = 9 model beyond the benchmark's parameters: one Rabi frequency om on every coupling
+    (om01, when given, on |01>-|0r> only), the detuning delta on both atoms, d0r more on |0r> only, the
+    blockade B, and the control entering as cos / sin(a x + b).  om01 != om or d0r != 0 make the two
+    2-level sectors differ (no twins) and leave the swap symmetry of {11, 1r, r1, rr} alone.
+    device=False: the same matrices as a closure over rydberg_hamiltonian_full."""
+    from robustgrape_amd.operators import FN_COS, FN_SIN, VAR_X, OperatorBasisHamiltonian, Term
+    o01 = om if om01 is None else om01
+    if device:
+        Hc = np.zeros((9, 9), np.complex128)
+        Hs = np.zeros((9, 9), np.complex128)
+        for r, c in ((1, 4), (2, 5), (3, 6), (3, 7), (6, 8), (7, 8)):  # RydbergTools.jl:118-130
+            s = 0.5 * (o01 if (r, c) == (1, 4) else om)
+            Hc[r, c] = Hc[c, r] = s
+            Hs[r, c], Hs[c, r] = -1j * s, 1j * s   # e^{-i phi} above the diagonal
+        terms = [Term(op=Hc, var=VAR_X, index=0, func=FN_COS, a=a, b=b),
+                 Term(op=Hs, var=VAR_X, index=0, func=FN_SIN, a=a, b=b)]
+        Hd = np.diag([0, 0, 0, 0, delta + d0r, delta, delta, delta, 2 * delta + B]).astype(np.complex128)
+        if np.any(Hd != 0):
+            terms.append(Term(op=Hd))
+        H0 = OperatorBasisHamiltonian(terms)
+        target = R.cz_full_target()
+    else:
+        def H0(t, p, xa):
+            phi = a * p[0] + b
+            H = R.rydberg_hamiltonian_full(phi, om, om, delta, delta, B)
+            H[1, 4] = np.exp(-1j * phi) * o01 / 2
+            H[4, 1] = np.exp(1j * phi) * o01 / 2
+            H[4, 4] += d0r
+            return H
+        target = lambda xa: R.cz_with_1q_phase_full(xa[0])  # noqa: E731
+    up = UnitaryRobustGRAPEProblem(t0=t0, ntimes=ntimes, ndim=9, H0=H0, nb_additional_param=1)
+    return FidelityRobustGRAPEProblem(up, W_FULL9, target)
+
+
+def relabel(fp, perm):
+    """The same physics with basis state i renamed perm[i]: every H0, error and target operator becomes
+    Pi op Pi^T and the projector Pi W Pi^T (Pi e_i = e_perm[i]); F and F_dx do not change.  The level
+    order inside the sectors does: the charges' order and the weighted level's in-sector index.
+    Operator-basis problems stay operator-basis; closures are wrapped."""
+    from robustgrape_amd.operators import (OperatorBasisError, OperatorBasisHamiltonian, OperatorBasisTarget, Term)
+    up = fp.unitary_problem
+    perm = np.asarray(perm, int)
+    assert sorted(perm.tolist()) == list(range(up.ndim))
+    Pi = np.zeros((up.ndim, up.ndim))
+    Pi[perm, np.arange(up.ndim)] = 1.0
+    rot = lambda M: Pi @ np.asarray(M, np.complex128) @ Pi.T  # noqa: E731
+    moved = lambda terms: [Term(op=rot(t.op), var=t.var, index=t.index, func=t.func, a=t.a, b=t.b,  # noqa: E731
+                                scale=t.scale) for t in terms]
+    if hasattr(up.H0, "terms"):
+        H0 = OperatorBasisHamiltonian(moved(up.H0.terms))
+        errs = [ErrorSource(OperatorBasisError(moved(es.Herror.terms))) for es in up.error_sources]
+        target = OperatorBasisTarget(moved(fp.target_unitary.terms))
+    else:
+        h, tgt = up.H0, fp.target_unitary
+        H0 = lambda t, p, xa: rot(h(t, p, xa))  # noqa: E731
+        errs = [ErrorSource(lambda t, p, xa, e, f=es.Herror: rot(f(t, p, xa, e))) for es in up.error_sources]
+        target = lambda xa: rot(tgt(xa))  # noqa: E731
+    W = (Pi @ np.asarray(fp.projector, np.float64) @ Pi.T)
+    return fp.replace(unitary_problem=up.replace(H0=H0, error_sources=errs), projector=W, target_unitary=target)
+
+
+def _swap(*pairs):
+    p = list(range(9))
+    for i, j in pairs:
+        p[i], p[j] = p[j], p[i]
+    return p
+
+
+# The phase-covariant walks' test family (tests/test_gauge_family_cpu.py, tests/test_gpu_gauge_family.py):
+# name -> (full9_family arguments, relabelling or None, expected (twin class B, ladder charges in both
+# classes) or None where the plan's report is taken as it comes).  Levels: |00>,|01>,|10>,|11>,|0r>,|r0>,
+# |1r>,|r1>,|rr> = 0..8.
+_DETUNED = dict(delta=0.7)
+_SCALED = dict(a=-2.5, b=0.7)
+_MIXED = dict(a=0.5, b=-1.1, delta=0.3, om=0.6, B=0.0, t0=T0_TEST)
+_UNEQUAL = dict(om01=0.8, d0r=0.4)
+GAUGE_FAMILY = {
+    "detuned": (_DETUNED, None, (True, True)),
+    "scaled": (_SCALED, None, (True, True)),
+    "mixed": (_MIXED, None, (True, True)),
+    "stiff": (dict(B=500.0, t0=3.0), None, (True, True)),   # |dt H|_1 ~ 16 at N_t = 96: squarings in E~
+    "unequal": (_UNEQUAL, None, (False, True)),
+    "swap-A": (_DETUNED, _swap((3, 8)), (True, False)),           # class A charges 2,1,0; c_A = 2
+    "swap-B2": (_SCALED, _swap((1, 4), (2, 5)), (True, False)),   # class B charges 1,0 twice; c_B = 1,1
+    "swap-B1": (_UNEQUAL, _swap((1, 4)), (False, False)),         # class B charges (1,0),(0,1); c_B = 1,0
+    "reversed": (_MIXED, [8 - i for i in range(9)], None),
+}
+
+
+def gauge_family_problem(case, ntimes, device=True):
+    """(the case's problem, the unrelabelled problem it was built from)."""
+    kw, perm, _ = GAUGE_FAMILY[case]
+    base = full9_family(ntimes, device=device, **kw)
+    return (base if perm is None else relabel(base, perm)), base
 
 
 def evered_pulse(ntimes=1000):
@@ -233,3 +331,28 @@ def as_closures(fp):
     errs = [ES(wrap_err(es.Herror)) for es in up.error_sources]
     up2 = up.replace(H0=lambda t, p, xa: h(t, p, xa), error_sources=errs)
     return fp.replace(unitary_problem=up2, target_unitary=lambda xa: tgt(xa))
+
+
+def weighted_indices(fp):
+    """{sector size: the weighted level's in-sector index c, per sector of that size, by first level}:
+    the sectors are the blocks of grape_symmetry_basis (host code), their levels in ascending order of the
+    rotated basis, the weight the diagonal of V^dag W V; None for a sector that has not exactly one
+    weighted level."""
+    import ctypes
+    from robustgrape_amd import _capi
+    from robustgrape_amd.operators import DescriptorBuffers
+    d = fp.unitary_problem.ndim
+    buf = DescriptorBuffers(fp, nparam=1, max_batch=1)
+    V = np.zeros(2 * d * d)
+    blk = (ctypes.c_int * d)()
+    rc = _capi.lib().grape_symmetry_basis(ctypes.byref(buf.desc), _capi.dptr(V), blk)
+    assert rc in (0, 1), rc
+    Vc = (V[0::2] + 1j * V[1::2]).reshape(d, d, order="F")
+    w = np.real(np.diag(Vc.conj().T @ np.asarray(fp.projector, np.float64) @ Vc))
+    blk = np.array(list(blk))
+    out = {}
+    for k in sorted(set(blk.tolist()), key=lambda k: int(np.flatnonzero(blk == k)[0])):
+        levels = np.flatnonzero(blk == k)
+        hit = [i for i, g in enumerate(levels) if abs(w[g]) > 1e-12]
+        out.setdefault(len(levels), []).append(hit[0] if len(hit) == 1 else None)
+    return out

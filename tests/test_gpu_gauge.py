@@ -49,18 +49,24 @@ def _check(test, F, Fdx, F0, g0, tier):
 
 def test_which_plans_are_phase_covariant():
     """Every Rydberg model with the phase as its control is, with or without its Rabi / detuning
-    error sources; NO_GAUGE, two controls per step and whole matrices are not."""
+    error sources; NO_GAUGE, two controls per step and whole matrices are not.  Ladder charges N_j = j
+    (sector_info()["ladder"], the compile-time charge differences of the merged walks): the 2- and 3-level
+    sectors in their natural level order; not the 4-level permutation sector {11, 1r, r1, rr} (charges
+    0, 1, 1, 2), nor the 3-level sector with |11> and |rr> exchanged (tests/problems.py swap-A: 2, 1, 0)."""
     from robustgrape_amd.operators import OPT_NO_GAUGE, OPT_NO_SECTORS, OPT_NO_SYMMETRY
-    cases = [(P.full9_problem(16), 0, 1, (True, True)), (P.full9_problem(16), OPT_NO_SYMMETRY, 1, (True, True)),
-             (P.sym_problem(16), 0, 1, (True,)), (P.fullblk_problem(16), 0, 1, (True,)),
-             (P.full9_problem(16), OPT_NO_GAUGE, 1, (False, False)),
-             (P.full9_problem(16, nerr=2), 0, 1, (True, True)),   # Rabi / detuning errors: covariant too
-             (P.full9_problem(16, nerr=2), OPT_NO_GAUGE, 1, (False, False)),
-             (P.full9_problem(16), OPT_NO_SECTORS, 1, (False,))]
-    for fp, opts, nparam, want in cases:
+    cases = [(P.full9_problem(16), 0, 1, (True, True), (True, True)),
+             (P.full9_problem(16), OPT_NO_SYMMETRY, 1, (True, True), (False, True)),
+             (P.sym_problem(16), 0, 1, (True,), (True,)), (P.fullblk_problem(16), 0, 1, (True,), (True,)),
+             (P.full9_problem(16), OPT_NO_GAUGE, 1, (False, False), (False, False)),
+             (P.full9_problem(16, nerr=2), 0, 1, (True, True), (False, True)),   # Rabi / detuning errors: covariant too
+             (P.full9_problem(16, nerr=2), OPT_NO_GAUGE, 1, (False, False), (False, False)),
+             (P.full9_problem(16), OPT_NO_SECTORS, 1, (False,), (False,)),
+             (P.gauge_family_problem("swap-A", 16)[0], 0, 1, (True, True), (False, True))]
+    for fp, opts, nparam, want, ladder in cases:
         pl = _plan(fp, 4, opts, nparam)
         try:
             assert pl.sector_info()["gauge"] == want, (opts, pl.sectors(), pl.sector_info())
+            assert pl.sector_info()["ladder"] == ladder, (opts, pl.sectors(), pl.sector_info())
         finally:
             pl.close()
 
@@ -164,6 +170,9 @@ def _check_err(test, out, b, ref, tier):
     ("full9-2err", lambda: P.full9_problem(40, nerr=2)),
     ("sym5-amp-freq", lambda: P.sym_problem(24, errors=("amp", "freq"))),
     ("fullblk7-amp-freq", lambda: P.fullblk_problem(24, errors=("amp", "freq"))),
+    # general charges (every level and error term renamed i -> 8 - i) and a non-zero diagonal in the lab-frame walks
+    ("full9-2err-reversed", lambda: P.relabel(P.full9_problem(40, nerr=2), [8 - i for i in range(9)])),
+    ("sym5-amp-freq-detuned", lambda: P.sym_problem(24, errors=("amp", "freq"), delta=0.4)),
 ])
 @pytest.mark.parametrize("batch", [3, 300])
 def test_gauge_image_walk_matches_per_step_exponentials_and_oracle(name, fp, batch):

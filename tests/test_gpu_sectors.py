@@ -230,25 +230,30 @@ def test_sectors_two_controls(monkeypatch):
     H0 = OperatorBasisHamiltonian(list(R.rydberg_full_operator_basis().terms)
                                   + [Term(Nr, var=VAR_X, index=1, func=FN_LINEAR, scale=0.3)])
     up = UnitaryRobustGRAPEProblem(t0=P.T0_TO, ntimes=nt, ndim=9, H0=H0, nb_additional_param=1)
-    fp = FidelityRobustGRAPEProblem(up, P.W_FULL9, R.cz_full_target())
     rng = np.random.default_rng(77)
     X = np.stack([np.concatenate([rng.uniform(-3, 3, 2 * nt), [rng.uniform(0, 6)]]) for _ in range(3)])
     from robustgrape_amd.engine import GrapePlan
     from robustgrape_amd.operators import OPT_NO_SECTORS
-    ps = GrapePlan(fp, nparam=2, device=0, max_batch=3)
-    pw = GrapePlan(fp, nparam=2, device=0, max_batch=3, options=OPT_NO_SECTORS)
-    try:
-        # the detuning control keeps the swap symmetry; the dark level (1r - r1)/sqrt2 now has a
-        # diagonal (Nr = 1 there): a 1-level sector in the 2-level class
-        assert ps.sectors() == ((3, 1), (2, 3)) and pw.sectors() == ((9, 1),)
-        out, ref = ps.fidelity_grad(X), pw.fidelity_grad(X)
-    finally:
-        ps.close()
-        pw.close()
-    _close(out, ref, P.fd_tier(fp, X, nparam=2))
-    Hc = lambda t, x, xa: H0(t, x, xa)  # noqa: E731  (closure form for the oracle)
-    fo = FidelityRobustGRAPEProblem(UnitaryRobustGRAPEProblem(t0=P.T0_TO, ntimes=nt, ndim=9, H0=Hc,
-                                                              nb_additional_param=1),
-                                    P.W_FULL9, lambda xa: R.cz_with_1q_phase_full(xa[0]))
-    F0, g0 = O.calculate_fidelity_and_derivatives(fo, X[1])[:2]
-    _close((out[0][1], out[1][1]), (F0, g0), P.fd_tier(fp, X, nparam=2))
+    # the detuning control keeps the swap symmetry; the dark level (1r - r1)/sqrt2 now has a diagonal
+    # (Nr = 1 there).  Weighted (|1r> and |r1> at 1/2 each: the rotated projector stays diagonal) it is a
+    # 1-level sector in the 2-level class; without weight its phase reaches neither F nor a derivative
+    # and the sector layout leaves it out (grape_engine.hip find_sectors, idle_levels)
+    W_dark = P.W_FULL9.copy()
+    W_dark[6, 6] = W_dark[7, 7] = 0.5
+    for W, layout in ((W_dark, ((3, 1), (2, 3))), (P.W_FULL9, P.FULL9_SYM)):
+        fp = FidelityRobustGRAPEProblem(up, W, R.cz_full_target())
+        ps = GrapePlan(fp, nparam=2, device=0, max_batch=3)
+        pw = GrapePlan(fp, nparam=2, device=0, max_batch=3, options=OPT_NO_SECTORS)
+        try:
+            assert ps.sectors() == layout and pw.sectors() == ((9, 1),), (ps.sectors(), pw.sectors())
+            out, ref = ps.fidelity_grad(X), pw.fidelity_grad(X)
+        finally:
+            ps.close()
+            pw.close()
+        _close(out, ref, P.fd_tier(fp, X, nparam=2))
+        Hc = lambda t, x, xa: H0(t, x, xa)  # noqa: E731  (closure form for the oracle)
+        fo = FidelityRobustGRAPEProblem(UnitaryRobustGRAPEProblem(t0=P.T0_TO, ntimes=nt, ndim=9, H0=Hc,
+                                                                  nb_additional_param=1),
+                                        W, lambda xa: R.cz_with_1q_phase_full(xa[0]))
+        F0, g0 = O.calculate_fidelity_and_derivatives(fo, X[1])[:2]
+        _close((out[0][1], out[1][1]), (F0, g0), P.fd_tier(fp, X, nparam=2))
