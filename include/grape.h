@@ -40,7 +40,7 @@ extern "C" {
 typedef enum grape_status {
     GRAPE_OK = 0,
     GRAPE_ERR_INVALID = -1,     /* bad descriptor / shape (reference: AssertionError, UnitaryCalculations.jl:22) */
-    GRAPE_ERR_UNSUPPORTED = -2, /* valid but outside this engine (e.g. ndim > GRAPE_MAX_SMALL_DIM) */
+    GRAPE_ERR_UNSUPPORTED = -2, /* valid but outside this engine (e.g. ndim > GRAPE_MAX_TILED_DIM) */
     GRAPE_ERR_ALLOC = -3,       /* device or host allocation failed */
     GRAPE_ERR_HIP = -4,         /* a HIP runtime call failed */
     GRAPE_ERR_SINGULAR = -5,    /* singular Pade denominator (Julia: SingularException from gesv!) */
@@ -57,6 +57,19 @@ typedef enum grape_status {
  * generator at these dimensions: the general path over the dense engine's
  * pivoted exponential (grape_dense.hpp gj_solve_pivot). */
 #define GRAPE_MAX_DENSE_DIM 64
+/* Largest dimension served at all: the tiled (MFMA, matrices in HBM) engine, used for
+ * GRAPE_MAX_DENSE_DIM < ndim <= GRAPE_MAX_TILED_DIM (zero-padded to a multiple of 16).  It serves
+ * grape_fidelity_grad, grape_fidelity_grad_device_async and grape_expm_batch for operator-basis
+ * problems with a Hermitian H0 (terms on 1, x or the step index), a diagonal projector, a target
+ * that may read x_add, and no error sources.  Refused there with GRAPE_ERR_UNSUPPORTED at plan
+ * creation: error sources, H0 terms that read x_add, a non-diagonal projector,
+ * GRAPE_OPT_GENERAL_H0 / a non-Hermitian H0, GRAPE_DESC_HOST_TABLES; on a tiled plan: the
+ * analysis entry points (grape_unitary_derivs, the interaction operators, the expectation
+ * values) and the time slices.  A tiled plan sizes the evaluations of one pass by a byte budget
+ * (at most max_batch); larger calls run as several passes with identical arithmetic.  Its calls
+ * read one word back from the device per pass, so grape_fidelity_grad_device_async synchronises
+ * the plan's stream once per pass before its last launches are enqueued. */
+#define GRAPE_MAX_TILED_DIM 128
 
 /*
  * Operator-basis description of the reference's Hamiltonian closures.
@@ -535,17 +548,20 @@ int grape_symmetry_basis(const grape_desc *desc, double *V, int *block);
 
 /*
  * Batched matrix exponential exp(A) of n column-major ndim x ndim complex
- * matrices (2 <= ndim <= GRAPE_MAX_DENSE_DIM; above GRAPE_MAX_SMALL_DIM the
+ * matrices (2 <= ndim <= GRAPE_MAX_TILED_DIM; above GRAPE_MAX_SMALL_DIM the
  * dense engine's solve needs a skew-Hermitian A, see grape_dense.hpp) on `device`, with the reference's algorithm (Julia
  * LinearAlgebra.exp!: Pade degree by 1-norm, gesv, squaring).  Host buffers.
- * stats (optional, 5 ints) receives how many matrices used Pade m=3,5,7,9,13.
+ * Above GRAPE_MAX_DENSE_DIM the tiled engine's solve-free exponential runs (Taylor of A / 2^s with
+ * |A / 2^s|_1 <= 0.95, then s squarings; grape_tiled.hpp): the result agrees with exp! to rounding.
+ * stats (optional, 5 ints) receives how many matrices used Pade m=3,5,7,9,13 (above
+ * GRAPE_MAX_SMALL_DIM: Julia's degree choice for |A|_1, the same histogram on every engine).
  * For a general A above GRAPE_MAX_SMALL_DIM use grape_expm_batch_general.
  */
 int grape_expm_batch(int device, int ndim, int n, const double *A, double *E, int *stats);
 
 /*
  * ABI 12: the same for ANY A (same layout, same stats).  GRAPE_MAX_SMALL_DIM < ndim <=
- * GRAPE_MAX_DENSE_DIM runs the dense engine's pivoted kernel (partial pivoting in the Pade
+ * GRAPE_MAX_DENSE_DIM (not above: GRAPE_ERR_UNSUPPORTED) runs the dense engine's pivoted kernel (partial pivoting in the Pade
  * solve, Julia's scaling s = ceil(log2(|A|_1 / 5.4))); smaller ndim runs the small engine's
  * exponential as grape_expm_batch does.  A is not balanced on the device: m (stats) and s follow
  * the 1-norm of A as given.

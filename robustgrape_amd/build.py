@@ -25,8 +25,9 @@ LBFGS = os.path.join(CSRC, "grape_lbfgs.hip")
 PROJ = os.path.join(CSRC, "grape_projector.hip")
 WALK = os.path.join(CSRC, "grape_walk_inst.hip")
 EVAL1 = os.path.join(CSRC, "grape_eval1.hip")
+TILED = os.path.join(CSRC, "grape_tiled.hip")
 DIMS = list(range(2, 13))  # GRAPE_DIMS in grape_launch.hpp; GRAPE_MAX_SMALL_DIM = 12
-SOURCES = [ENGINE, INST, DENSE, UNITARY, LBFGS, PROJ, WALK, EVAL1]
+SOURCES = [ENGINE, INST, DENSE, UNITARY, LBFGS, PROJ, WALK, EVAL1, TILED]
 # every source and header of the library (an #include of a file that is not here would not reach source_id():
 # tests/test_capi_cpu.py checks the includes), the C ABI last
 DEPS = sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".hip", ".hpp"))) + \
@@ -92,7 +93,9 @@ def _units(defines):
              # the chunk walks: no MachineLICM (grape_walk.hpp explains the register budget)
              (WALK, ["-mllvm", "-disable-machine-licm"], os.path.join(sub, "grape_walk.o")),
              # the one-workgroup-per-evaluation kernel (latency-bound calls): the walks' arithmetic
-             (EVAL1, ["-mllvm", "-disable-machine-licm"], os.path.join(sub, "grape_eval1.o"))]
+             (EVAL1, ["-mllvm", "-disable-machine-licm"], os.path.join(sub, "grape_eval1.o")),
+             # the tiled engine (64 < d <= 128): a unit of its own, plain flags
+             (TILED, [], os.path.join(sub, "grape_tiled.o"))]
     units += [(INST, [f"-DGRAPE_INST_DIM={d}"], os.path.join(sub, f"grape_inst_d{d}.o")) for d in DIMS]
     return sub, units
 

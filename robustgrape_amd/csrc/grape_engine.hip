@@ -28,6 +28,7 @@
 #include "grape.h"
 #include "grape_launch.hpp"
 #include "grape_dense_api.hpp"
+#include "grape_tiled_api.hpp"
 #include "grape_unitary_api.hpp"
 #include "grape_symmetry.hpp"
 #include "grape_eval1_api.hpp"
@@ -252,6 +253,12 @@ struct grape_plan {
            *dn_M = nullptr, *dn_Mc = nullptr, *dn_Z = nullptr, *dn_Ub = nullptr, *dn_Zl = nullptr, *dn_Vc = nullptr,
            *dn_Sx = nullptr, *dn_Tot = nullptr, *dn_Me = nullptr, *dn_Mp = nullptr, *dn_B0 = nullptr,
            *dn_Fadd = nullptr, *dn_Fd2add = nullptr;
+    // tiled engine (GRAPE_MAX_DENSE_DIM < d <= GRAPE_MAX_TILED_DIM): the problem and the workspace of one pass
+    // of max_batch evaluations (max_batch: the caller's, cut to what the plan's byte budget holds)
+    bool tiled = false;
+    grape_tiled::TiledProblem TP{};
+    grape_tiled::TiledBatch TB{};
+    int *tl_h_smax = nullptr;  // pinned: the pass's largest squaring count
     // grape_unitary_derivs workspace (allocated on first use)
     grape::VSpec *ud_vs = nullptr;
     cd *ud_E = nullptr, *ud_C = nullptr, *ud_V = nullptr, *ud_S = nullptr, *ud_out = nullptr;
@@ -338,6 +345,7 @@ static void free_plan(grape_plan *p) {
     if (p->ev_fork) (void)hipEventDestroy(p->ev_fork);
     if (p->ev_join) (void)hipEventDestroy(p->ev_join);
     if (p->h_status) (void)hipHostFree(p->h_status);
+    if (p->tl_h_smax) (void)hipHostFree(p->tl_h_smax);
     delete p;
 }
 
@@ -1048,6 +1056,112 @@ static int create_dense(const grape_desc *desc, grape_plan *p, bool xadd_dep, co
 }
 
 // ---------------------------------------------------------------------------
+// tiled engine plan (GRAPE_MAX_DENSE_DIM < d <= GRAPE_MAX_TILED_DIM; grape_tiled.hip)
+// ---------------------------------------------------------------------------
+// column-major interleaved d x d complex <-> zero-padded row-major planes (re, then im) of P x P
+static void to_tiled_image(const double *src, int d, double *img) {
+    const int P = grape_tiled::padded_dim(d);
+    const size_t plane = (size_t)P * P;
+    std::fill(img, img + 2 * plane, 0.0);
+    for (int j = 0; j < d; ++j)
+        for (int i = 0; i < d; ++i) {
+            img[(size_t)i * P + j] = src[2 * ((size_t)i + (size_t)j * d)];
+            img[plane + (size_t)i * P + j] = src[2 * ((size_t)i + (size_t)j * d) + 1];
+        }
+}
+static void from_tiled_image(const double *img, int d, double *dst) {
+    const int P = grape_tiled::padded_dim(d);
+    const size_t plane = (size_t)P * P;
+    for (int j = 0; j < d; ++j)
+        for (int i = 0; i < d; ++i) {
+            dst[2 * ((size_t)i + (size_t)j * d)] = img[(size_t)i * P + j];
+            dst[2 * ((size_t)i + (size_t)j * d) + 1] = img[plane + (size_t)i * P + j];
+        }
+}
+
+// A tiled plan's workspace is sized by bytes, not by max_batch x everything: a quarter of the budget (at most
+// kTiledSlabItems items) holds the slab of the exponential and of the gradient's eps-variants, the rest the
+// evaluations of one pass (E and Q: 2 N_t images each, 512 MB at P = 128, N_t = 1 024).  A call of more
+// evaluations than fit runs as several passes with identical arithmetic.
+constexpr size_t kTiledBudgetBytes = (size_t)6 << 30;
+constexpr size_t kTiledSlabItems = 1024;
+constexpr size_t kTiledSlabImages = 9;  // A, A^2, A^3, A^4, two Horner buffers, E', Q_{k-1} M'_c, Y^dag
+
+// slab of the exponential: `items` images in each of the six buffers, from one allocation
+static hipError_t alloc_exp_slab(grape_setup::DevicePool &mem, size_t items, size_t img, grape_tiled::ExpSlab &X,
+                                 double **extra, size_t n_extra) {
+    double *base = nullptr;
+    const hipError_t e = mem.alloc(&base, (6 + n_extra) * items * img);
+    if (e != hipSuccess) return e;
+    X.slab = (int)items;
+    double **slots[6] = {&X.A, &X.A2, &X.A3, &X.A4, &X.B0, &X.B1};
+    for (int i = 0; i < 6; ++i) *slots[i] = base + (size_t)i * items * img;
+    for (size_t i = 0; i < n_extra; ++i) extra[i] = base + (6 + i) * items * img;
+    return hipSuccess;
+}
+
+static int create_tiled(const grape_desc *desc, grape_plan *p, const ProjectorSetup &ps) {
+    const int D = desc->ndim;
+    p->tiled = true;
+    grape_tiled::TiledProblem &TP = p->TP;
+    DevProblem &P = TP.P;
+    fill_problem_scalars(desc, ps.trP, P);
+    const std::vector<grape::VSpec> vs = set_variants(P, 0, false);  // nominal only: the eps-variants are never kept
+    P.nv = 1;
+    P.nvg = P.np;
+    TP.Pd = grape_tiled::padded_dim(D);
+    // scan chunking: ~sqrt(N_t) chunks, as the dense engine
+    const int nc = (int)std::ceil(std::sqrt((double)P.Nt));
+    TP.Lc = (P.Nt + nc - 1) / nc;
+    TP.Nc = (P.Nt + TP.Lc - 1) / TP.Lc;
+    const size_t IMG = grape_tiled::image_doubles(D), imgB = IMG * sizeof(double);
+    const size_t Nt = P.Nt, Nc = TP.Nc, nh = 1 + (size_t)P.na;
+    const size_t eval_imgs = 2 * Nt + 3 * Nc + 4 + 2 * nh;
+    size_t slab = std::min<size_t>(kTiledSlabItems, std::max<size_t>(1, kTiledBudgetBytes / 4 / (kTiledSlabImages * imgB)));
+    slab = std::min(slab, (size_t)p->max_batch * Nt);
+    const size_t slabB = slab * kTiledSlabImages * imgB;
+    const size_t fit = kTiledBudgetBytes > slabB ? (kTiledBudgetBytes - slabB) / (eval_imgs * imgB) : 0;
+    if (fit < 1)
+        return fail(GRAPE_ERR_ALLOC, "tiled engine: one evaluation needs " + std::to_string(eval_imgs * imgB + slabB) +
+                                         " bytes of workspace, the plan's budget is " + std::to_string(kTiledBudgetBytes));
+    p->max_batch = (int)std::min<size_t>(p->max_batch, fit);
+    const size_t MB = p->max_batch;
+    grape_tiled::TiledBatch &B = p->TB;
+    double *opimg = nullptr, *W = nullptr, *extra[3] = {nullptr, nullptr, nullptr};
+    bool ok = p->mem.alloc(&opimg, (size_t)desc->n_ops * IMG) == hipSuccess && p->mem.alloc(&W, (size_t)TP.Pd) == hipSuccess &&
+              p->mem.alloc(&B.E, MB * Nt * IMG) == hipSuccess && p->mem.alloc(&B.Q, MB * Nt * IMG) == hipSuccess &&
+              p->mem.alloc(&B.Carry, MB * Nc * IMG) == hipSuccess && p->mem.alloc(&B.Tm, MB * Nc * IMG) == hipSuccess &&
+              p->mem.alloc(&B.Mc, MB * Nc * IMG) == hipSuccess && p->mem.alloc(&B.U, MB * IMG) == hipSuccess &&
+              p->mem.alloc(&B.M, MB * IMG) == hipSuccess && p->mem.alloc(&B.WK, MB * IMG) == hipSuccess &&
+              p->mem.alloc(&B.T, MB * IMG) == hipSuccess && p->mem.alloc(&B.U0, MB * nh * IMG) == hipSuccess &&
+              p->mem.alloc(&B.K, MB * nh * IMG) == hipSuccess && p->mem.alloc(&B.tau, 2 * MB) == hipSuccess &&
+              p->mem.alloc(&B.ctl, MB * Nt) == hipSuccess && p->mem.alloc(&B.smax, (size_t)1) == hipSuccess &&
+              alloc_exp_slab(p->mem, slab, IMG, B.X, extra, 3) == hipSuccess &&
+              p->mem.alloc(&p->d_x, MB * P.nx) == hipSuccess && p->mem.alloc(&p->d_F, MB) == hipSuccess &&
+              p->mem.alloc(&p->d_Fdx, MB * P.nx) == hipSuccess && p->mem.alloc(&p->d_ctrl, kCtrlInts) == hipSuccess;
+    if (!ok) return fail(GRAPE_ERR_ALLOC, "device allocation failed (tiled)");
+    B.Ev = extra[0];
+    B.Ts = extra[1];
+    B.Yd = extra[2];
+    if (hipHostMalloc(reinterpret_cast<void **>(&p->tl_h_smax), sizeof(int), hipHostMallocDefault) != hipSuccess)
+        return fail(GRAPE_ERR_ALLOC, "pinned allocation failed (tiled)");
+    B.h_smax = p->tl_h_smax;
+    std::vector<double> img((size_t)desc->n_ops * IMG), Wp(TP.Pd, 0.0);
+    for (int o = 0; o < desc->n_ops; ++o) to_tiled_image(desc->ops + 2 * (size_t)o * D * D, D, img.data() + o * IMG);
+    for (int i = 0; i < D; ++i) Wp[i] = ps.W[i];
+    if (hipMemset(p->d_ctrl, 0, kCtrlInts * sizeof(int)) != hipSuccess ||
+        hipMemcpy(opimg, img.data(), img.size() * sizeof(double), hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(W, Wp.data(), Wp.size() * sizeof(double), hipMemcpyHostToDevice) != hipSuccess)
+        return fail(GRAPE_ERR_HIP, "upload failed (tiled)");
+    if (int rc = upload_terms(p, desc, 0, vs, P, " (tiled)", " (tiled)")) return rc;
+    TP.opimg = opimg;
+    TP.W = W;
+    P.W = W;
+    p->P = P;  // the C ABI reads nx / np / ne from the plan's problem for every engine
+    return GRAPE_OK;
+}
+
+// ---------------------------------------------------------------------------
 // plan creation, phase by phase (grape_plan_create calls them top to bottom; each returns a GRAPE_*
 // code with the message set, and the caller frees the plan on any failure)
 // ---------------------------------------------------------------------------
@@ -1059,7 +1173,20 @@ static int validate_desc(const grape_desc *desc, int *n_err_terms) {
     if (D < 2 || desc->ntimes < 1 || desc->nparam < 1 || desc->nadd < 0 || desc->nerr < 0 ||
         (!tables && desc->n_ops < 1))
         return fail(GRAPE_ERR_INVALID, "bad dimensions in descriptor");
-    if (D > GRAPE_MAX_DENSE_DIM) return fail(GRAPE_ERR_UNSUPPORTED, "ndim > GRAPE_MAX_DENSE_DIM");
+    if (D > GRAPE_MAX_TILED_DIM) return fail(GRAPE_ERR_UNSUPPORTED, "ndim > GRAPE_MAX_TILED_DIM");
+    if (D > GRAPE_MAX_DENSE_DIM) {  // the tiled engine: what it does not serve is refused here, before any device work
+        if (tables)
+            return fail(GRAPE_ERR_UNSUPPORTED, "ndim > GRAPE_MAX_DENSE_DIM: closures (host tables) are served up to "
+                                               "GRAPE_MAX_DENSE_DIM levels");
+        if (desc->nerr > 0)
+            return fail(GRAPE_ERR_UNSUPPORTED, "ndim > GRAPE_MAX_DENSE_DIM: error sources are served up to "
+                                               "GRAPE_MAX_DENSE_DIM levels");
+        if (desc->reserved[1] & GRAPE_OPT_GENERAL_H0)
+            return fail(GRAPE_ERR_UNSUPPORTED, "ndim > GRAPE_MAX_DENSE_DIM: GRAPE_OPT_GENERAL_H0 is served up to "
+                                               "GRAPE_MAX_DENSE_DIM levels (the tiled engine needs a Hermitian H0)");
+        if (desc->n_h0_terms > grape_tiled::kMaxTerms || desc->n_target_terms > grape_tiled::kMaxTerms)
+            return fail(GRAPE_ERR_UNSUPPORTED, "ndim > GRAPE_MAX_DENSE_DIM: more than 256 H0 or target terms");
+    }
     if (tables) {  // above GRAPE_MAX_SMALL_DIM: the general path with the dense exponential of the tables
         if (!desc->projector_diag && !desc->projector) return fail(GRAPE_ERR_INVALID, "missing projector");
     } else {
@@ -1111,6 +1238,22 @@ static int choose_route(const grape_desc *desc, int n_err_terms, Route &rt) {
     // launch_table_variants).  Without the option nothing changes: a non-Hermitian H0 or error source
     // is refused above.
     rt.pivot = rt.general_h0 && D > GRAPE_MAX_SMALL_DIM;
+    if (D > GRAPE_MAX_DENSE_DIM) {  // the tiled engine (validate_desc refused closures, error sources, the general option)
+        for (int k = 0; k < desc->n_h0_terms; ++k)
+            if (desc->h0_terms[k].var == GRAPE_VAR_XADD)
+                return fail(GRAPE_ERR_UNSUPPORTED, "ndim > GRAPE_MAX_DENSE_DIM: H0 terms that read x_add are served up "
+                                                   "to GRAPE_MAX_DENSE_DIM levels");
+        if (desc->projector) {
+            const size_t n = (size_t)D;
+            for (size_t j = 0; j < n; ++j)
+                for (size_t i = 0; i < n; ++i) {
+                    const double *e = desc->projector + 2 * (i + j * n);
+                    if ((i != j && (e[0] != 0.0 || e[1] != 0.0)) || (i == j && e[1] != 0.0))
+                        return fail(GRAPE_ERR_UNSUPPORTED, "ndim > GRAPE_MAX_DENSE_DIM: a non-diagonal projector is "
+                                                           "served up to GRAPE_MAX_DENSE_DIM levels");
+                }
+        }
+    }
     // closures above the small engine: host tables through the general path (materialised
     // derivatives), each tabulated generator exponentiated by the dense engine (grape_dense.hip
     // launch_table_variants; the host checks that the tables are Hermitian)
@@ -1764,7 +1907,9 @@ int grape_plan_create(const grape_desc *desc, int device, grape_plan **out) {
 
     grape_plan *p = new grape_plan();
     int rc = open_plan(p, desc, device, rt);
-    if (!rc && desc->ndim > GRAPE_MAX_SMALL_DIM && !rt.tables && !rt.pivot) {
+    if (!rc && desc->ndim > GRAPE_MAX_DENSE_DIM) {
+        rc = create_tiled(desc, p, ps);
+    } else if (!rc && desc->ndim > GRAPE_MAX_SMALL_DIM && !rt.tables && !rt.pivot) {
         rc = create_dense(desc, p, rt.xadd_dep, ps, n_err_terms);
     } else if (!rc) {
         PlanBuild b{desc, p, rt, ps, n_err_terms};
@@ -1963,6 +2108,15 @@ static int enqueue(grape_plan *p, int nb, const double *d_x, double *d_F, double
     hipStream_t st = p->stream;
     p->cur_stream = st;
     const KMark mk = profiling_mark(p);
+    if (p->tiled) {  // one pass of nb <= max_batch evaluations in the plan's workspace (grape_tiled.hip)
+        grape_tiled::TiledBatch TB = p->TB;
+        TB.nb = nb;
+        TB.x = d_x;
+        TB.F = d_F;
+        TB.Fdx = d_Fdx;
+        HIPCHECK(grape_tiled::launch_pipeline(p->TP, TB, st, mk));
+        return GRAPE_OK;
+    }
     if (p->general_h0) return enqueue_general(p, nb, d_x, d_F, d_Fdx, d_Fd2, d_Fd2dx, mk);
     if (p->dense) {
         const grape_dense::DenseBatch DB = dense_batch(p, nb, d_x, d_F, d_Fdx, d_Fd2, d_Fd2dx);
@@ -2340,7 +2494,7 @@ static int graph_capture(grape_plan *p, int nb, hipGraphExec_t *out) {
 
 static bool graph_path(const grape_plan *p, int nbatch) {
     const bool disabled = (p->P.opts & GRAPE_OPT_NO_GRAPH) != 0;
-    return !disabled && !p->profiling && !p->tables && !p->general_h0 && nbatch > 0 && nbatch <= kGraphBatch &&
+    return !disabled && !p->profiling && !p->tables && !p->general_h0 && !p->tiled && nbatch > 0 && nbatch <= kGraphBatch &&
            nbatch <= p->max_batch;
 }
 
@@ -2434,6 +2588,7 @@ int grape_fidelity_grad(grape_plan *p, int nbatch, const double *x, double *F, d
 // Time sharding of one evaluation: see include/grape.h.
 static int slice_check(grape_plan *p) {
     if (!p) return fail(GRAPE_ERR_INVALID, "null plan");
+    if (p->tiled) return fail(GRAPE_ERR_UNSUPPORTED, "time slices: not served by the tiled engine (ndim > GRAPE_MAX_DENSE_DIM)");
     if (!p->dense || p->general_h0 || p->tables || p->P.ne > 0 || p->P.na > 0 || p->P.gen_proj || p->uses_tstep)
         return fail(GRAPE_ERR_UNSUPPORTED, "time slices: dense-engine operator-basis plans without error sources, "
                                            "x_add, a general projector or step-index terms");
@@ -2655,6 +2810,8 @@ static int ud_interaction(grape_plan *p, const double *x, const double *H0tab, c
 }
 
 static int analysis_check(grape_plan *p, bool tables_call, const char *what) {
+    if (p->tiled)  // (no dense kernel at the wrong size: the analysis kernels stop at GRAPE_MAX_DENSE_DIM)
+        return fail(GRAPE_ERR_UNSUPPORTED, std::string(what) + ": not served by the tiled engine (ndim > GRAPE_MAX_DENSE_DIM)");
     if (p->tables && !tables_call)
         return fail(GRAPE_ERR_INVALID, std::string(what) + ": host-table plan: use the _tables entry point");
     if (!p->tables && tables_call)
@@ -2792,6 +2949,7 @@ static int unitary_derivs(grape_plan *p, const double *x, const double *Htab, do
 int grape_unitary_derivs(grape_plan *p, const double *x, double *U, double *U_dx, double *U_dx_add, double *U_derr,
                          double *U_derr_dx, double *U_derr_dx_add) {
     if (!p || !x) return fail(GRAPE_ERR_INVALID, "null argument");
+    if (int rc = analysis_check(p, p->tables, "grape_unitary_derivs")) return rc;
     if (p->tables) return fail(GRAPE_ERR_INVALID, "grape_unitary_derivs: host-table plan: use grape_unitary_derivs_tables");
     return unitary_derivs(p, x, nullptr, U, U_dx, U_dx_add, U_derr, U_derr_dx, U_derr_dx_add);
 }
@@ -2828,13 +2986,46 @@ static int dense_expm_batch(int device, int ndim, int n, const double *A, double
     return GRAPE_OK;
 }
 
+// 64 < ndim <= 128: the tiled engine's solve-free exponential, in slabs of a byte budget
+static int tiled_expm_batch(int ndim, int n, const double *A, double *E, int *stats) {
+    const size_t IMG = grape_tiled::image_doubles(ndim);
+    std::vector<double> h((size_t)n * IMG);
+    for (int i = 0; i < n; ++i) to_tiled_image(A + 2 * (size_t)i * ndim * ndim, ndim, h.data() + i * IMG);
+    grape_setup::DevicePool mem;
+    double *dA = nullptr, *dE = nullptr;
+    int *dctl = nullptr, *dwords = nullptr, *h_smax = nullptr;
+    grape_tiled::ExpSlab X{};
+    const size_t slab = std::min<size_t>((size_t)n, std::max<size_t>(1, ((size_t)1 << 30) / (6 * IMG * sizeof(double))));
+    if (mem.alloc(&dA, n * IMG) || mem.alloc(&dE, n * IMG) || mem.alloc(&dctl, (size_t)n) || mem.alloc(&dwords, (size_t)8) ||
+        alloc_exp_slab(mem, slab, IMG, X, nullptr, 0))
+        return fail(GRAPE_ERR_ALLOC, "device allocation failed");
+    if (hipHostMalloc(reinterpret_cast<void **>(&h_smax), sizeof(int), hipHostMallocDefault) != hipSuccess)
+        return fail(GRAPE_ERR_ALLOC, "pinned allocation failed");
+    int words[8] = {0};
+    const bool ok = hipMemcpy(dA, h.data(), h.size() * sizeof(double), hipMemcpyHostToDevice) == hipSuccess &&
+                    hipMemset(dwords, 0, 8 * sizeof(int)) == hipSuccess &&
+                    grape_tiled::launch_expm_raw(ndim, dA, dE, n, X, dctl, dwords, h_smax, dwords + 2, nullptr) == hipSuccess &&
+                    hipDeviceSynchronize() == hipSuccess &&
+                    hipMemcpy(h.data(), dE, h.size() * sizeof(double), hipMemcpyDeviceToHost) == hipSuccess &&
+                    hipMemcpy(words, dwords, 8 * sizeof(int), hipMemcpyDeviceToHost) == hipSuccess;
+    (void)hipHostFree(h_smax);
+    if (!ok) return fail(GRAPE_ERR_HIP, std::string("tiled expm batch failed: ") + hipGetErrorString(hipGetLastError()));
+    for (int i = 0; i < n; ++i) from_tiled_image(h.data() + i * IMG, ndim, E + 2 * (size_t)i * ndim * ndim);
+    if (stats)
+        for (int k = 0; k < 5; ++k) stats[k] = words[2 + k];
+    return GRAPE_OK;
+}
+
 static int expm_batch(int device, int ndim, int n, const double *A, double *E, int *stats, bool pivot) {
-    if (ndim < 2 || ndim > GRAPE_MAX_DENSE_DIM) return fail(GRAPE_ERR_UNSUPPORTED, "ndim outside [2, GRAPE_MAX_DENSE_DIM]");
+    const int dmax = pivot ? GRAPE_MAX_DENSE_DIM : GRAPE_MAX_TILED_DIM;  // (the pivoted exponential stays the dense engine's)
+    if (ndim < 2 || ndim > dmax)
+        return fail(GRAPE_ERR_UNSUPPORTED, pivot ? "ndim outside [2, GRAPE_MAX_DENSE_DIM]" : "ndim outside [2, GRAPE_MAX_TILED_DIM]");
     if (n < 0 || (n > 0 && (!A || !E))) return fail(GRAPE_ERR_INVALID, "bad argument");
     if (n == 0) return GRAPE_OK;
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return fail(GRAPE_ERR_NO_DEVICE, "no HIP device");
     HIPCHECK(hipSetDevice(device));
+    if (ndim > GRAPE_MAX_DENSE_DIM) return tiled_expm_batch(ndim, n, A, E, stats);
     if (ndim > GRAPE_MAX_SMALL_DIM) return dense_expm_batch(device, ndim, n, A, E, stats, pivot);
     const size_t T = (size_t)ndim * ndim;
     grape_setup::DevicePool mem;
