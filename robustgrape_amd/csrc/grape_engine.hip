@@ -2090,15 +2090,14 @@ static int enqueue_wide(grape_plan *p, int nb, const double *d_x, double *d_F, d
     H.F = d_F;
     H.Fdx = d_Fdx;
     H.tgt_part = p->d_tgt_part;
-    const int a_first = ma == 0 ? 1 : 0;
     mk(GRAPE_KERNEL_WALK_FWD, 0);
-    HIPCHECK(grape_walk::launch_merged_wide(0, Pw[0], Bw[0], Pw[1], Bw[1], a_first, st));
+    HIPCHECK(grape_walk::launch_merged_wide(0, Pw[0], Bw[0], Pw[1], Bw[1], st));
     mk(GRAPE_KERNEL_WALK_FWD, 1);
     mk(GRAPE_KERNEL_SCAN, 0);
     HIPCHECK(grape_proj::launch_sector_head(H, nb, st));
     mk(GRAPE_KERNEL_SCAN, 1);
     mk(GRAPE_KERNEL_WALK_GRAD, 0);
-    HIPCHECK(grape_walk::launch_merged_wide(1, Pw[0], Bw[0], Pw[1], Bw[1], a_first, st));
+    HIPCHECK(grape_walk::launch_merged_wide(1, Pw[0], Bw[0], Pw[1], Bw[1], st));
     mk(GRAPE_KERNEL_WALK_GRAD, 1);
     return GRAPE_OK;
 }
@@ -2197,11 +2196,11 @@ static int enqueue(grape_plan *p, int nb, const double *d_x, double *d_F, double
             if (p->merged && s < 2) {  // both classes in one lane (throughput passes)
                 const int ma = p->merge_pa, mb = 1 - ma;
                 mk(s == 0 ? GRAPE_KERNEL_WALK_FWD : GRAPE_KERNEL_WALK_GRAD, 0);
-                hipError_t e = grape_walk::launch_merged(s, p->Ps[ma], Bc[ma], p->Ps[mb], Bc[mb], ma == 0 ? 1 : 0, st);
+                hipError_t e = grape_walk::launch_merged(s, p->Ps[ma], Bc[ma], p->Ps[mb], Bc[mb], st);
                 mk(s == 0 ? GRAPE_KERNEL_WALK_FWD : GRAPE_KERNEL_WALK_GRAD, 1);
                 if (e == hipSuccess && s == 0) {  // the merged walks' sequential scan (lane-minor totals)
                     mk(GRAPE_KERNEL_SCAN, 0);
-                    e = grape_walk::launch_merged(2, p->Ps[ma], Bc[ma], p->Ps[mb], Bc[mb], ma == 0 ? 1 : 0, st);
+                    e = grape_walk::launch_merged(2, p->Ps[ma], Bc[ma], p->Ps[mb], Bc[mb], st);
                     mk(GRAPE_KERNEL_SCAN, 1);
                 }
                 return e;

@@ -44,7 +44,7 @@ hipError_t launch_pair(int stage, const grape::DevProblem &P0, const grape::DevB
                        const grape::DevBatch &B1, hipStream_t st);
 // Throughput passes of the same layout with phase-covariant classes at equal chunking: ONE lane walks
 // both classes of an (evaluation, chunk) (k_walk_fwd_m / k_walk_grad_m); the gradient stage writes
-// one F_dx part, class 0's + class 1's (a_first: class A is the plan's class 0), into class A's
+// one F_dx part, the sum of the two classes' (either order gives the same double), into class A's
 // sec_part.  Stage 0: k_walk_fwd_m (chunk totals, lane-minor), stage 2: k_scan_seq (carries and U
 // from them), stage 1: k_walk_grad_m, which writes the F_dx rows itself (no k_sec_reduce for such passes).
 // merged_ok tells whether the classes fit.
@@ -57,7 +57,7 @@ hipError_t fill_gauge_base(const grape::DevProblem &P, int nsec, grape::cd *scr,
 // complex per base matrix)
 hipError_t fill_gauge_err_base(const grape::DevProblem &P, int nsec, grape::cd *scr, grape::cd *out, hipStream_t st);
 hipError_t launch_merged(int stage, const grape::DevProblem &PA, const grape::DevBatch &BA, const grape::DevProblem &PB,
-                         const grape::DevBatch &BB, int a_first, hipStream_t st);
+                         const grape::DevBatch &BB, hipStream_t st);
 // The wide pass of a rank-one merged plan (grape_walk.hpp, "The wide pass"): one lane per evaluation over all
 // N_t steps, BA.nb evaluations, no chunks and no scan.  Stage 0: k_walk_fwd_m<..., WIDE> walks psi = U e_c forward
 // and writes the head's U blocks (BA.Ub / BB.Ub: column c filled, the rest zero); stage 1: k_walk_grad_m<..., WIDE>
@@ -67,7 +67,7 @@ hipError_t launch_merged(int stage, const grape::DevProblem &PA, const grape::De
 constexpr int kWideMaxNt = 4096;
 bool wide_ok(const grape::DevProblem &PA, const grape::DevProblem &PB);
 hipError_t launch_merged_wide(int stage, const grape::DevProblem &PA, const grape::DevBatch &BA, const grape::DevProblem &PB,
-                              const grape::DevBatch &BB, int a_first, hipStream_t st);
+                              const grape::DevBatch &BB, hipStream_t st);
 // F_dx parts the class's gradient stage writes per evaluation: its sectors, or (k_walk_grad with several
 // sectors per lane, no error sources) one pre-summed part per lane row (grape_walk.hpp walk_grad_body)
 int grad_parts(const grape::DevProblem &P);

@@ -1,8 +1,11 @@
 // grape_walk_gauge.hpp -- helpers of the phase-covariant classes (a piece of grape_walk.hpp): the charges
-// (GaugeN), the per-step phase base (gauge_cis, cis_m1), the pair phases and difference weights (gauge_phases,
+// (GaugeN), the per-step phase base (gauge_cis, gauge_cis_tab, cis_m1), the pair phases and difference weights (gauge_phases,
 // gauge_fd_weights_dn and their ladder forms), E~ of a workgroup's sectors (gauge_base, gauge_base_lds) and
 // E_k = D_k E~ D_k^dag (gauge_sandwich, gauge_prop).  No kernel lives here; the chunk, merged, image and
-// lab-frame walks and grape_eval1.hip all take their phases from this file, so they agree bit for bit.
+// lab-frame walks and grape_eval1.hip all take their phases and products from this file, so kernels that share
+// a phase base agree bit for bit (the merged family has its own, gauge_cis_tab).  The products of the phases with
+// each other and with E~ are fused (cmulf): the reference never forms D_k E~ D_k^dag, so there is no product of
+// its own to mirror, and the fused form has one rounding fewer per component.
 #pragma once
 #include "grape_cis.hpp"
 #include "grape_walk_core.hpp"
@@ -48,12 +51,13 @@ __device__ __forceinline__ cd gauge_pow(cd z, int n) {
     cd r = cmake(1.0, 0.0);
     if (n > 0) r = z;
 #pragma unroll 1
-    for (int m = 1; m < n; ++m) r = cmul(r, z);
+    for (int m = 1; m < n; ++m) r = cmulf(r, z);
     return r;
 }
 // p = e^{i t}: the per-step phase base of the phase-covariant walks (grape_cis.hpp: Cody-Waite reduction
-// and fdlibm kernels, <= 0.67 ulp; the library sincos above |t| = 1e5).  Every gauge kernel (forward,
-// gradient, image walk, eval1) takes its phases here, so the walks of one evaluation agree bit for bit.
+// and fdlibm kernels, at most 1 unit of 2^-52 (tests/test_cis_cpu.py); the library sincos above |t| = 1e5).  Every
+// gauge kernel outside the merged family (forward, gradient, image walk, eval1) takes its phases here, so the walks
+// of one evaluation agree bit for bit.
 // the constants of grape_cis::cis_fast as opaque SGPR pairs: an empty asm hides the literal from the
 // instruction selector, so each Horner step is one v_fma_f64 with a scalar operand (not a v_fmac_f64 on
 // a VGPR copy of the literal, two v_mov_b32 per constant and step: the walks are built without
@@ -68,6 +72,22 @@ struct CisConst {
 __device__ __forceinline__ cd gauge_cis(double t) {
     double s, c;
     if (fabs(t) <= grape_cis::kCisFast) grape_cis::cis_fast(t, s, c, CisConst());
+    else sincos(t, &s, &c);
+    return cmake(c, s);
+}
+// The merged walks' p = e^{i t} (grape_cis::cis_tab: reduction by pi / 64, a 128-entry table, two short
+// polynomials; the library sincos above |t| = 5e4): 28 VALU instructions where gauge_cis takes 46, a fifth of a wide
+// step's.  Every form of k_walk_fwd_m / k_walk_grad_m takes its phase here and no other kernel does, so the merged
+// family agrees with itself bit for bit and with the other families to rounding.  gauge_cis_stage copies the table
+// (2 KB) from global memory to the workgroup's LDS before the first step; every lane of the workgroup must call it.
+static __device__ const grape_cis::CisTabEntry kCisTableDev[grape_cis::kCisTabN] = {GRAPE_CIS_TABLE_ENTRIES};
+__device__ __forceinline__ void gauge_cis_stage(grape_cis::CisTabEntry *tab) {
+    for (int i = threadIdx.x; i < grape_cis::kCisTabN; i += blockDim.x) tab[i] = kCisTableDev[i];
+    __syncthreads();
+}
+__device__ __forceinline__ cd gauge_cis_tab(double t, const grape_cis::CisTabEntry *tab) {
+    double s, c;
+    if (fabs(t) <= grape_cis::kCisTabFast) grape_cis::cis_tab(t, tab, s, c, CisConst());
     else sincos(t, &s, &c);
     return cmake(c, s);
 }
@@ -99,7 +119,7 @@ __device__ __forceinline__ void gauge_fd_weights_dn(cd q, const GaugeN<D> &g, cd
             const int dn = g.n[r] - g.n[j], m = dn < 0 ? -dn : dn;
             cd z = q;
 #pragma unroll 1
-            for (int i = 1; i < m; ++i) z = cadd(cadd(z, q), cmul(q, z));
+            for (int i = 1; i < m; ++i) z = cadd(cadd(z, q), cmulf(q, z));
             f[gauge_pair(D, r, j)] = m == 0 ? czero() : cmake(z.re, dn < 0 ? -z.im : z.im);
         }
     }
@@ -186,7 +206,7 @@ __device__ __forceinline__ void gauge_phases(cd p, const GaugeN<D> &g, cd (&e)[k
 // d_j M_jk conj(d_k) = M_jk e_jk (e_jj = 1: the diagonal unchanged)
 template <int D>
 __device__ __forceinline__ cd gauge_sandwich(const cd (&e)[kGaugePairs<D>], int j, int k, cd m) {
-    return j == k ? m : j < k ? cmul(m, e[gauge_pair(D, j, k)]) : cmul(m, cconj(e[gauge_pair(D, k, j)]));
+    return j == k ? m : j < k ? cmulf(m, e[gauge_pair(D, j, k)]) : cmulf(m, cconj(e[gauge_pair(D, k, j)]));
 }
 // E_k = D_k E~ D_k^dag; the diagonal is E~'s own
 template <int D, class Store>
@@ -206,13 +226,13 @@ template <int D>
 __device__ __forceinline__ void ladder_powers(cd z, cd (&pw)[D]) {  // pw[m] = z^m (gauge_pow's product order)
     pw[0] = cmake(1.0, 0.0);
 #pragma unroll
-    for (int m = 1; m < D; ++m) pw[m] = m == 1 ? z : cmul(pw[m - 1], z);
+    for (int m = 1; m < D; ++m) pw[m] = m == 1 ? z : cmulf(pw[m - 1], z);
 }
 template <int D>
 __device__ __forceinline__ void ladder_rho(cd q, cd (&rh)[D]) {  // rho(m) = (1 + q)^m - 1 (gauge_fd_weights_dn)
     rh[0] = czero();
 #pragma unroll
-    for (int m = 1; m < D; ++m) rh[m] = m == 1 ? q : cadd(cadd(rh[m - 1], q), cmul(q, rh[m - 1]));
+    for (int m = 1; m < D; ++m) rh[m] = m == 1 ? q : cadd(cadd(rh[m - 1], q), cmulf(q, rh[m - 1]));
 }
 template <int D>
 __device__ __forceinline__ void gauge_phases_ladder(cd p, cd (&e)[kGaugePairs<D>]) {

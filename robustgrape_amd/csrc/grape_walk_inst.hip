@@ -184,7 +184,7 @@ void merged_variant(const grape::DevProblem &PA, const grape::DevProblem &PB, Go
         lad ? go(I3{}, std::false_type{}, std::true_type{}) : go(I3{}, std::false_type{}, std::false_type{});
 }
 hipError_t launch_merged(int stage, const grape::DevProblem &PA, const grape::DevBatch &BA, const grape::DevProblem &PB,
-                         const grape::DevBatch &BB, int a_first, hipStream_t st) {
+                         const grape::DevBatch &BB, hipStream_t st) {
     if (!merged_ok(PA, PB)) return hipErrorInvalidValue;
     const long lanes = (long)BA.nb * PA.nchunks;  // (class A: one sector, BA.nb evaluations)
     const dim3 grid((unsigned)((lanes + grape::kWalkBlock - 1) / grape::kWalkBlock)), blk(grape::kWalkBlock);
@@ -200,9 +200,9 @@ hipError_t launch_merged(int stage, const grape::DevProblem &PA, const grape::De
             hipLaunchKernelGGL((grape::k_scan_seq<DA, TW>), dim3((unsigned)((BA.nb + grape::kSeqBlock - 1) / grape::kSeqBlock)), dim3(grape::kSeqBlock), 0, st, PA,
                                BA, PB, BB, BA.nb);
         } else if (r1) {
-            hipLaunchKernelGGL((grape::k_walk_grad_m<DA, TW, LAD, true>), grid, blk, 0, st, PA, BA, PB, BB, a_first);
+            hipLaunchKernelGGL((grape::k_walk_grad_m<DA, TW, LAD, true>), grid, blk, 0, st, PA, BA, PB, BB);
         } else {
-            hipLaunchKernelGGL((grape::k_walk_grad_m<DA, TW, LAD, false>), grid, blk, 0, st, PA, BA, PB, BB, a_first);
+            hipLaunchKernelGGL((grape::k_walk_grad_m<DA, TW, LAD, false>), grid, blk, 0, st, PA, BA, PB, BB);
         }
     };
     merged_variant(PA, PB, go);
@@ -213,7 +213,7 @@ bool wide_ok(const grape::DevProblem &PA, const grape::DevProblem &PB) {
     return merged_ok(PA, PB) && PA.rank1 && PB.rank1 && PA.gauge_Et && PB.gauge_Et && PA.Nt <= kWideMaxNt;
 }
 hipError_t launch_merged_wide(int stage, const grape::DevProblem &PA, const grape::DevBatch &BA, const grape::DevProblem &PB,
-                              const grape::DevBatch &BB, int a_first, hipStream_t st) {
+                              const grape::DevBatch &BB, hipStream_t st) {
     if (!wide_ok(PA, PB) || (stage != 0 && stage != 1)) return hipErrorInvalidValue;
     const dim3 grid((unsigned)((BA.nb + grape::kWalkBlock - 1) / grape::kWalkBlock)), blk(grape::kWalkBlock);
     auto go = [&](auto da, auto tw, auto lad) {
@@ -221,7 +221,7 @@ hipError_t launch_merged_wide(int stage, const grape::DevProblem &PA, const grap
         constexpr bool TW = decltype(tw)::value;
         constexpr bool LAD = decltype(lad)::value;
         if (stage == 0) hipLaunchKernelGGL((grape::k_walk_fwd_m<DA, TW, LAD, true>), grid, blk, 0, st, PA, BA, PB, BB);
-        else hipLaunchKernelGGL((grape::k_walk_grad_m<DA, TW, LAD, true, true>), grid, blk, 0, st, PA, BA, PB, BB, a_first);
+        else hipLaunchKernelGGL((grape::k_walk_grad_m<DA, TW, LAD, true, true>), grid, blk, 0, st, PA, BA, PB, BB);
     };
     merged_variant(PA, PB, go);
     return hipGetLastError();

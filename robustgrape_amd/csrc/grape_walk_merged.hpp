@@ -18,10 +18,11 @@ namespace grape {
 // (evaluation, chunk) repeat the same per-step work: the load of x_k, e^{i a x_k}, e^{i phi} - 1,
 // the loop.  A merged lane walks class A (one sector of DA levels) and class B (two 2-level
 // sectors, twins or not) over the same chunk, sharing that work, and its gradient walk writes ONE
-// F_dx part, (0 + part_A) + part_B in the plan's class order -- the value k_sec_reduce would have
-// formed from the two parts -- so the reduction reads one part.  Per class the operations are the
-// gauge walks' own (walk_fwd_body / walk_grad_body with GAUGE): at equal chunking the results are
-// those of the per-class kernels bit for bit.  Both classes take class A's chunking (the engine
+// F_dx part, part_A + part_B -- the value k_sec_reduce would have formed from the two parts in either class
+// order -- so the reduction reads one part.  Per class the operations are the
+// gauge walks' own (walk_fwd_body / walk_grad_body with GAUGE) but for the step phase e^{i a x_k}, which
+// the merged kernels take from a table in LDS (gauge_cis_tab): at equal chunking the results are those of
+// the per-class kernels to rounding.  Both classes take class A's chunking (the engine
 // sets class B's L and nchunks to class A's).
 // E~ of the merged walks (round 6; SMEM of gauge_prop_lds): from the plan's global copy
 // (DevProblem::gauge_Et) through scalar loads -- E~ is launch-uniform, so each entry is an SGPR operand of the
@@ -174,6 +175,8 @@ __device__ __forceinline__ void wide_fwd_body(const DevProblem &PA, const DevBat
                                               const DevBatch &BB) {
     constexpr int NEB = TWB ? 1 : 2;
     __shared__ double xtile[kWalkBlock][kFdxTile + 1];  // (+1: conflict-free rows)
+    __shared__ grape_cis::CisTabEntry ctab[grape_cis::kCisTabN];
+    gauge_cis_stage(ctab);
     const WideLane L = wide_lane(BA);
     GaugeN<DA> gA[1];
     GaugeN<2> gB[NEB];
@@ -190,7 +193,7 @@ __device__ __forceinline__ void wide_fwd_body(const DevProblem &PA, const DevBat
         for (int j = 0; j < 2; ++j) psiB[w][j] = cmake(j == PB.rank1_c[w] ? 1.0 : 0.0, 0.0);
     }
     auto step = [&](double xk) {
-        const cd p1 = gauge_cis(PA.gauge_a * xk);
+        const cd p1 = gauge_cis_tab(PA.gauge_a * xk, ctab);
         wide_step_fwd<DA, 1, LAD>(PA.gauge_Et, gA, p1, psiA);
         wide_step_fwd<2, NEB, LAD>(PB.gauge_Et, gB, p1, psiB);
     };
@@ -223,6 +226,8 @@ __global__ __launch_bounds__(kWalkBlock, (WIDE ? GRAPE_WALK_WIDE_FWD_WAVES : GRA
         return;
     }
     constexpr int NEB = TWB ? 1 : 2;
+    __shared__ grape_cis::CisTabEntry ctab[grape_cis::kCisTabN];
+    gauge_cis_stage(ctab);
     const VBlock vb = hw_block();
     const WalkLane L = walk_lane<1>(PA, BA, vb);  // (class A: one sector; its chunking is both classes')
     const double *xt = BA.x + (size_t)L.be * PA.nx;  // this evaluation's row of x
@@ -252,7 +257,7 @@ __global__ __launch_bounds__(kWalkBlock, (WIDE ? GRAPE_WALK_WIDE_FWD_WAVES : GRA
         const int k = min(k0 + jj, PA.Nt - 1);
         const double xk = xn.v0;
         xn = walk_load_x(1, xt + (size_t)min(k + 1, PA.Nt - 1));  // next step's control
-        const cd p1 = gauge_cis(PA.gauge_a * xk);  // e^{i a x_k}, both classes (the engine checks one a)
+        const cd p1 = gauge_cis_tab(PA.gauge_a * xk, ctab);  // e^{i a x_k}, both classes (the engine checks one a)
         merged_step_fwd<DA, 1, LAD>(EtA, gA, p1, QA);
         merged_step_fwd<2, NEB, LAD>(EtB, gB, p1, QB);
     };
@@ -260,7 +265,7 @@ __global__ __launch_bounds__(kWalkBlock, (WIDE ? GRAPE_WALK_WIDE_FWD_WAVES : GRA
     // chunk run unpredicated and the rest only in the other chunks' lanes (a branch, not selects)
     const int nlast = PA.Nt - (PA.nchunks - 1) * PA.L;
     // unrolled by hand (two steps per trip, then the odd one: no loop-carried register moves): the phases'
-    // constants pass through an inline asm (gauge_cis), which LLVM treats as convergent and will not runtime-unroll
+    // constants pass through an inline asm (gauge_cis_tab), which LLVM treats as convergent and will not runtime-unroll
     int j2 = 0;
 #pragma unroll 1
     for (; j2 + 1 < nlast; j2 += 2) {
@@ -743,7 +748,8 @@ __device__ __forceinline__ void wide_grad_init(const cd *u, const cd *a, const c
 }
 template <int DA, bool TWB, bool LAD>
 __device__ __forceinline__ void wide_grad_body(const DevProblem &PA, const DevBatch &BA, const DevProblem &PB,
-                                               const DevBatch &BB, int a_first, double (*ftile)[kFdxTile + 1], int2 *frow) {
+                                               const DevBatch &BB, double (*ftile)[kFdxTile + 1], int2 *frow,
+                                               const grape_cis::CisTabEntry *ctab) {
     constexpr int NEB = TWB ? 1 : 2;
     constexpr int NXB = (TWB && GRAPE_WALK_TWIN_SUM) ? 1 : 2;
     const WideLane L = wide_lane(BA);
@@ -763,13 +769,10 @@ __device__ __forceinline__ void wide_grad_body(const DevProblem &PA, const DevBa
     for (int w = 0; w < NEB; ++w) gB[w] = gauge_charges<2>(PB, w);
     auto step = [&](double xk) {  // one step of both classes: the F_dx value, in the plan's class order
         const double xe = xk + PA.eps;
-        const cd p1 = gauge_cis(PA.gauge_a * xk), q = cis_m1(PA.gauge_a * (xe - xk));
+        const cd p1 = gauge_cis_tab(PA.gauge_a * xk, ctab), q = cis_m1(PA.gauge_a * (xe - xk));
         const double sa = wide_step_grad<DA, 1, 1, LAD>(PA.gauge_Et, gA, p1, q, PA.inv_eps, psiA, phiA);
         const double sb = wide_step_grad<2, NEB, NXB, LAD>(PB.gauge_Et, gB, p1, q, PB.inv_eps, psiB, phiB);
-        double v = 0.0;
-        v += a_first ? sa : sb;
-        v += a_first ? sb : sa;
-        return v;
+        return sa + sb;  // (the classes' parts in either order: see k_walk_grad_m's step)
     };
     // The tiles and the steps of a tile in descending order.  One workgroup tile serves both ways: it arrives
     // holding the tile's controls (wide_load_x), each lane replaces x_k in its row by the step's F_dx value, and the
@@ -794,12 +797,14 @@ __device__ __forceinline__ void wide_grad_body(const DevProblem &PA, const DevBa
 }
 template <int DA, bool TWB, bool LAD, bool R1, bool WIDE = false>
 __global__ __launch_bounds__(kWalkBlock, (WIDE ? GRAPE_WALK_WIDE_GRAD_WAVES : R1 ? GRAPE_WALK_R1_WAVES : GRAPE_WALK_MERGED_WAVES)) void k_walk_grad_m(DevProblem PA, DevBatch BA,
-                                                                                   DevProblem PB, DevBatch BB, int a_first) {
+                                                                                   DevProblem PB, DevBatch BB) {
     constexpr int NEB = TWB ? 1 : 2;
     __shared__ double ftile[kWalkBlock][kFdxTile + 1];  // (the F_dx tile; +1: conflict-free rows)
     __shared__ int2 frow[kWalkBlock];                   // each row's evaluation and first step
+    __shared__ grape_cis::CisTabEntry ctab[grape_cis::kCisTabN];
+    gauge_cis_stage(ctab);
     if constexpr (WIDE) {
-        wide_grad_body<DA, TWB, LAD>(PA, BA, PB, BB, a_first, ftile, frow);
+        wide_grad_body<DA, TWB, LAD>(PA, BA, PB, BB, ftile, frow, ctab);
         return;
     }
     const VBlock vb = hw_block();
@@ -858,7 +863,7 @@ __global__ __launch_bounds__(kWalkBlock, (WIDE ? GRAPE_WALK_WIDE_GRAD_WAVES : R1
         const int k = min(k0 + jj, PA.Nt - 1);
         const double xk = xn.v0, xe = xk + PA.eps;  // the reference's perturbed control
         xn = walk_load_x(1, xt + (size_t)min(k + 1, PA.Nt - 1));  // next step's control
-        const cd p1 = gauge_cis(PA.gauge_a * xk), q = cis_m1(PA.gauge_a * (xe - xk));  // (xe - xk: exact)
+        const cd p1 = gauge_cis_tab(PA.gauge_a * xk, ctab), q = cis_m1(PA.gauge_a * (xe - xk));  // (xe - xk: exact)
         double sa, sb;
         if constexpr (R1) {
             sa = merged_step_grad_r1<DA, 1, 1, LAD>(EtA, gA, p1, q, PA.inv_eps, psiA, phiA);
@@ -867,10 +872,11 @@ __global__ __launch_bounds__(kWalkBlock, (WIDE ? GRAPE_WALK_WIDE_GRAD_WAVES : R1
             sa = merged_step_grad<DA, 1, 1, LAD>(EtA, gA, p1, q, PA.inv_eps, XA);
             sb = merged_step_grad<2, NEB, NXB, LAD>(EtB, gB, p1, q, PB.inv_eps, XB);
         }
-        double v = 0.0;  // k_sec_reduce's sum of the classes' parts, in the plan's class order
-        v += a_first ? sa : sb;
-        v += a_first ? sb : sa;
-        return v;
+        // k_sec_reduce's sum of the classes' parts, (0 + part_0) + part_1 in the plan's class order: whichever class
+        // is the plan's first, that is sa + sb -- 0 + a is a, addition commutes in IEEE arithmetic, and the one
+        // exception (0 + -0 = +0) only turns a -0 sum of two -0 parts into +0, the same value -- so the lane adds
+        // once instead of selecting the order (4 v_cndmask and an add per step)
+        return sa + sb;
     };
     // F_dx straight to its [evaluation][n_x] row through a workgroup tile of kFdxTile steps: the
     // lanes of a workgroup hold consecutive evaluations, so a flush writes 16 lanes' kFdxTile-long
