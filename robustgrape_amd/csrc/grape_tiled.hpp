@@ -37,6 +37,7 @@
 #include <hip/hip_runtime.h>
 
 #include "grape_kernels.hpp"
+#include "grape_tiled_ctl.hpp"
 
 namespace grape_tiled {
 
@@ -190,35 +191,7 @@ __constant__ const double kInvFact[21] = {1.0, 1.0, 0.5, 1.0 / 6, 1.0 / 24, 1.0 
                                           1.0 / 355687428096000.0, 1.0 / 6402373705728000.0,
                                           1.0 / 121645100408832000.0, 1.0 / 2432902008176640000.0};
 
-// The dense engine's Taylor degree rule (grape_dense.hpp taylor_degree: the lowest of 8 / 12 / 16 / 20 whose
-// remainder bound is at most 2^-53 at that 1-norm) as the index `top` of the highest Paterson-Stockmeyer
-// block below the initial one: degree = 4 (top + 2).
-__device__ __forceinline__ int taylor_top(double nA) {
-    if (nA <= 0.069) return 0;
-    if (nA <= 0.335) return 1;
-    if (nA <= 0.826) return 2;
-    return 3;
-}
-// Julia's Pade degree for |A|_1 as a histogram slot (m = 3, 5, 7, 9, 13): the stats of grape_expm_batch
-__device__ __forceinline__ int julia_m_index(double nA) {
-    if (nA <= 0.015) return 0;
-    if (nA <= 0.25) return 1;
-    if (nA <= 0.95) return 2;
-    if (nA <= 2.1) return 3;
-    return 4;
-}
-// ctl word of an item: Taylor block index | squaring count << 2.  s is the smallest count that brings
-// |A / 2^s|_1 to at most 0.95, the end of the solve-free regime.
-__device__ __forceinline__ int make_ctl(double nA) {
-    int s = 0;
-    if (nA > 0.95) {
-        s = (int)ceil(log2(nA / 0.95));
-        if (s < 0) s = 0;
-        while (s > 0 && ldexp(nA, -(s - 1)) <= 0.95) --s;
-        while (ldexp(nA, -s) > 0.95) ++s;
-    }
-    return taylor_top(ldexp(nA, -s)) | (s << 2);
-}
+// (taylor_top, julia_m_index, make_ctl: grape_tiled_ctl.hpp, host-testable)
 
 // Workgroup sum / max in a fixed order (deterministic); red: NTHREADS doubles of LDS
 __device__ __forceinline__ double wg_sum(double v, double *red) {

@@ -333,6 +333,86 @@ def as_closures(fp):
     return fp.replace(unitary_problem=up2, target_unitary=lambda xa: tgt(xa))
 
 
+def tiled_rich_problem(d, x0s, weights, small, nparam=3, x_add=(0.3, -0.7)):
+    """(problem, x) of the tiled engine's wider test family (tests/test_gpu_tiled_edges.py): what
+    synthetic.dense_problem never has.  Six Hermitian Ginibre operators H_i = synthetic._hermitian(d, 400 + i),
+    |H_i|_1 = 1, dt = 0.5, one step per entry of x0s:
+
+        H(k, x) = small H_0 + x[0] H_1 + small (cos(1.3 x[1] + 0.2) H_2 + sin(1.3 x[1] + 0.2) H_3)
+                  + small (0.5 k - 1) H_4 + small x[2] H_5           (k = 1 .. N_t, the step index)
+
+    so every term kind the engine serves (ONE, LINEAR, COS, SIN; on 1, x and the step index) with np = 3; nparam = 1
+    drops the terms on x[1] and x[2].  x ~ U[-1, 1) (seed 5) with x[:, 0] = x0s: |A_k|_1 is 0.5 |x0s[k]| plus a
+    rest of order small.  Target with na = 2: Q (I - e_0 e_0^T - e_l e_l^T) + cis(x_add[0]) Q e_0 e_0^T +
+    cis(2 x_add[1] + 0.1) Q e_l e_l^T, l = d - 1 the last level.  Projector: diagonal, {level: weight}."""
+    from robustgrape_amd import synthetic as S
+    from robustgrape_amd.operators import (FN_CIS, FN_COS, FN_LINEAR, FN_SIN, VAR_TSTEP, VAR_X, VAR_XADD,
+                                           OperatorBasisHamiltonian, OperatorBasisTarget, Term)
+    assert nparam in (1, 3)
+    H = [S._hermitian(d, 400 + i) for i in range(6)]
+    terms = [Term(small * H[0]), Term(H[1], var=VAR_X, index=0, func=FN_LINEAR)]
+    if nparam == 3:
+        terms += [Term(small * H[2], var=VAR_X, index=1, func=FN_COS, a=1.3, b=0.2),
+                  Term(small * H[3], var=VAR_X, index=1, func=FN_SIN, a=1.3, b=0.2)]
+    terms.append(Term(small * H[4], var=VAR_TSTEP, func=FN_LINEAR, a=0.5, b=-1.0))
+    if nparam == 3:
+        terms.append(Term(small * H[5], var=VAR_X, index=2, func=FN_LINEAR))
+    ntimes = len(x0s)
+    up = UnitaryRobustGRAPEProblem(t0=0.5 * ntimes, ntimes=ntimes, ndim=d, H0=OperatorBasisHamiltonian(terms),
+                                   nb_additional_param=2)
+    Q = S.dense_target(d)
+    P0, Pl = np.zeros((d, d)), np.zeros((d, d))
+    P0[0, 0] = Pl[d - 1, d - 1] = 1.0
+    target = OperatorBasisTarget([Term(Q @ (np.eye(d) - P0 - Pl)),
+                                  Term(Q @ P0, var=VAR_XADD, index=0, func=FN_CIS),
+                                  Term(Q @ Pl, var=VAR_XADD, index=1, func=FN_CIS, a=2.0, b=0.1)])
+    W = np.zeros(d)
+    for level, w in weights.items():
+        W[level] = w
+    x = np.random.default_rng(5).uniform(-1.0, 1.0, size=(ntimes, 3))[:, :nparam].copy()
+    x[:, 0] = x0s
+    return FidelityRobustGRAPEProblem(up, np.diag(W), target), np.concatenate([x.ravel(), np.asarray(x_add, float)])
+
+
+def tiled_sixteen_weights(d):
+    """Sixteen scattered projector weights, unequal, in both row tiles (0-63 and the remainder), on both sides of
+    every 16-row fragment edge below d, on the last level and on d - 17 and d - 2."""
+    mid = 50 if d < 100 else 65
+    return {0: 1.0, 3: 0.5, 15: 2.0, 16: 1.5, 17: 0.25, 31: 1.0, 40: 1.0, 47: 0.75, 48: 1.25, mid: 1.0, 62: 1.0,
+            63: 0.5, 64: 1.5, d - 17: 2.0, d - 2: 0.25, d - 1: 1.0}
+
+
+TILED_X0S = (0.3, -0.8, 1.2, 0.5, -1.0)   # five steps of Taylor 12 / 16 / 16 / 12 / 16 with small = 0.1
+SEAM_D, SEAM_NT, SEAM_EVALS = 65, 43, 24   # 1 032 steps in one pass: slabs of 1 024 + 8
+
+
+def seam_batch():
+    """(problem, X) of the slab-seam test: 24 evaluations of dense_problem(65, 43, rank 16)."""
+    from robustgrape_amd import synthetic as S
+    X = np.stack([S.dense_x(SEAM_NT, seed=700 + s) for s in range(SEAM_EVALS)])
+    return S.dense_problem(SEAM_D, SEAM_NT, rank=16), X
+
+
+def tiled_edge_case(name):
+    """(problem, x, nparam) of a case of the fixture tests/golden/tiled_edges.npz (make_golden_tiled_edges.py)."""
+    if name == "proj113":   # the sixteen weights at P = 128 != d, remainder tile of 49 live rows
+        fp, x = tiled_rich_problem(113, TILED_X0S, tiled_sixteen_weights(113), 0.1)
+        return fp, x, 3
+    if name == "seam23":    # the last evaluation of the seam batch: the slab seam falls at its step 35
+        fp, X = seam_batch()
+        return fp, X[SEAM_EVALS - 1], 2
+    raise KeyError(name)
+
+
+def step_norms(fp, x, nparam):
+    """|dt H(k, x_k, x_add)|_1 of every step of one control vector (the norms k_tctl computes)."""
+    up = fp.unitary_problem
+    na = up.nb_additional_param
+    xm, xa = x[:len(x) - na].reshape(up.ntimes, nparam), x[len(x) - na:]
+    dt = up.t0 / up.ntimes
+    return np.array([dt * np.abs(np.asarray(up.H0(k + 1, xm[k], xa))).sum(axis=0).max() for k in range(up.ntimes)])
+
+
 def weighted_indices(fp):
     """{sector size: the weighted level's in-sector index c, per sector of that size, by first level}:
     the sectors are the blocks of grape_symmetry_basis (host code), their levels in ascending order of the
