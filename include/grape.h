@@ -104,8 +104,28 @@ typedef enum grape_func {
     GRAPE_FN_CIS = 4     /* f(t) = cos t + i sin t  (target terms only) */
 } grape_func;
 
+/*
+ * Product coefficients (an addition within ABI 12: GRAPE_OP_FACTOR, no layout change).  A term whose
+ * op is GRAPE_OP_FACTOR carries no operator: its real value scale_re * f(a*v + b) multiplies the
+ * coefficient of the closest preceding operator term of the same list, so that
+ *
+ *     c_t = scale_t f_t(a_t v_t + b_t) * prod_j  s_j g_j(a_j w_j + b_j)      (at most GRAPE_MAX_FACTORS j)
+ *
+ * states an amplitude x phase drive  Omega_k (cos phi_k Hc + sin phi_k Hs), an envelope w(k) x_k (a
+ * factor on GRAPE_VAR_TSTEP) or a global scale x_add[q] x_k.  Factor terms are allowed in h0_terms and
+ * err_terms only, never first in a list or in an error source's range; func is ONE, LINEAR, COS or
+ * SIN; scale_im must be 0; var / index as for any term.  n_h0_terms and err_term_offsets count them.
+ * The finite differences of the reference perturb every occurrence of a variable: x cos x is
+ * differentiated in both places.  Plans with factor terms are served up to GRAPE_MAX_SMALL_DIM levels
+ * (GRAPE_ERR_UNSUPPORTED above) by the stored-intermediate kernels: sectors, symmetry-adapted sectors,
+ * error sources, any projector, a non-Hermitian H0 and the analysis entry points, not the chunk walks
+ * or the one-workgroup kernel (grape_plan_eval1, grape_plan_rank1 and grape_plan_wide return 0).
+ */
+#define GRAPE_OP_FACTOR (-1)
+#define GRAPE_MAX_FACTORS 2
+
 typedef struct grape_term {
-    int32_t op;        /* index into grape_desc.ops */
+    int32_t op;        /* index into grape_desc.ops, or GRAPE_OP_FACTOR */
     int32_t var;       /* grape_var */
     int32_t index;     /* parameter index for GRAPE_VAR_X / GRAPE_VAR_XADD */
     int32_t func;      /* grape_func */

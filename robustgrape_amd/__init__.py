@@ -9,7 +9,7 @@ compute_unitary_and_derivatives) are aliases.
 """
 from .types import (ErrorSource, FidelityRobustGRAPEParameters, FidelityRobustGRAPEProblem,
                     UnitaryRobustGRAPEProblem)
-from .operators import (OperatorBasisError, OperatorBasisHamiltonian, OperatorBasisTarget, Term,
+from .operators import (Factor, OperatorBasisError, OperatorBasisHamiltonian, OperatorBasisTarget, Term,
                         FN_CIS, FN_COS, FN_LINEAR, FN_ONE, FN_SIN, VAR_ONE, VAR_TSTEP, VAR_X, VAR_XADD)
 from .engine import (GrapePlan, calculate_fidelity_and_derivatives, calculate_unitary_and_derivatives,
                      clear_plans, get_plan)
@@ -29,7 +29,7 @@ __all__ = [
     "LBFGS", "GradientDescent",
     "ErrorSource", "UnitaryRobustGRAPEProblem", "FidelityRobustGRAPEProblem", "FidelityRobustGRAPEParameters",
     "calculate_fidelity_and_derivatives", "calculate_unitary_and_derivatives", "GrapePlan", "get_plan",
-    "clear_plans", "OperatorBasisHamiltonian", "OperatorBasisError", "OperatorBasisTarget", "Term",
+    "clear_plans", "OperatorBasisHamiltonian", "OperatorBasisError", "OperatorBasisTarget", "Term", "Factor",
     "RydbergTools", "regularization_cost", "regularization_cost_phase", "optimize_fidelity_and_error_sources",
     "optimize_restarts", "calculate_interaction_error_operators", "calculate_expectation_values",
     "calculate_fidelity_response", "calculate_fidelity_response_fft", "OptimizationResult", "minimizer", "minimum", "FidelityOptimProblem", "compute_fidelity_and_gradient", "compute_unitary_and_derivatives",

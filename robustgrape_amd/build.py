@@ -19,6 +19,7 @@ LIB = os.path.join(HERE, "libgrape.so")
 OBJ = os.path.join(HERE, "_obj")
 ENGINE = os.path.join(CSRC, "grape_engine.hip")
 INST = os.path.join(CSRC, "grape_inst.hip")
+PROD = os.path.join(CSRC, "grape_prod_inst.hip")
 DENSE = os.path.join(CSRC, "grape_dense.hip")
 UNITARY = os.path.join(CSRC, "grape_unitary.hip")
 LBFGS = os.path.join(CSRC, "grape_lbfgs.hip")
@@ -27,7 +28,7 @@ WALK = os.path.join(CSRC, "grape_walk_inst.hip")
 EVAL1 = os.path.join(CSRC, "grape_eval1.hip")
 TILED = os.path.join(CSRC, "grape_tiled.hip")
 DIMS = list(range(2, 13))  # GRAPE_DIMS in grape_launch.hpp; GRAPE_MAX_SMALL_DIM = 12
-SOURCES = [ENGINE, INST, DENSE, UNITARY, LBFGS, PROJ, WALK, EVAL1, TILED]
+SOURCES = [ENGINE, INST, PROD, DENSE, UNITARY, LBFGS, PROJ, WALK, EVAL1, TILED]
 # every source and header of the library (an #include of a file that is not here would not reach source_id():
 # tests/test_capi_cpu.py checks the includes), the C ABI last
 DEPS = sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".hip", ".hpp"))) + \
@@ -97,6 +98,8 @@ def _units(defines):
              # the tiled engine (64 < d <= 128): a unit of its own, plain flags
              (TILED, [], os.path.join(sub, "grape_tiled.o"))]
     units += [(INST, [f"-DGRAPE_INST_DIM={d}"], os.path.join(sub, f"grape_inst_d{d}.o")) for d in DIMS]
+    # the product-coefficient kernels (grape_prod.hpp), a unit of their own per dimension
+    units += [(PROD, [f"-DGRAPE_INST_DIM={d}"], os.path.join(sub, f"grape_prod_d{d}.o")) for d in DIMS]
     return sub, units
 
 

@@ -147,12 +147,13 @@ hipError_t dispatch_dim(int D, F &&f) {
     }
     return hipErrorInvalidValue;
 }
-hipError_t dispatch_pipeline(int D, const DevProblem &P, const DevBatch &B, hipStream_t st, const KMark &mk) {
-    return dispatch_dim(D, [&](auto d) { return launch_pipeline<decltype(d)::value>(P, B, st, mk); });
+hipError_t dispatch_pipeline(int D, const DevProblem &P, const DevBatch &B, const grape::FactorTab &F, hipStream_t st,
+                             const KMark &mk) {
+    return dispatch_dim(D, [&](auto d) { return launch_pipeline<decltype(d)::value>(P, B, F, st, mk); });
 }
-hipError_t dispatch_sector_stage(int S, int stage, const DevProblem &P, const DevBatch &B, hipStream_t st,
-                                 const KMark &mk) {
-    return dispatch_dim(S, [&](auto d) { return grape_host::launch_sector_stage<decltype(d)::value>(stage, P, B, st, mk); });
+hipError_t dispatch_sector_stage(int S, int stage, const DevProblem &P, const DevBatch &B, const grape::FactorTab &F,
+                                 hipStream_t st, const KMark &mk) {
+    return dispatch_dim(S, [&](auto d) { return grape_host::launch_sector_stage<decltype(d)::value>(stage, P, B, F, st, mk); });
 }
 hipError_t dispatch_sector_reduce(int S, const DevProblem &P, const DevBatch &B, const grape::SecParts &sp, int nev,
                                   hipStream_t st, const KMark &mk) {
@@ -162,8 +163,9 @@ hipError_t dispatch_expm_raw(int D, const cd *A, cd *E, int n, int *ovf, int *ov
                              int *mstats, hipStream_t st) {
     return dispatch_dim(D, [&](auto d) { return launch_expm_raw<decltype(d)::value>(A, E, n, ovf, ovfc, status, mstats, st); });
 }
-hipError_t dispatch_expm_variants(int D, const DevProblem &P, const DevBatch &B, hipStream_t st) {
-    return dispatch_dim(D, [&](auto d) { return grape_host::launch_expm_variants<decltype(d)::value>(P, B, st); });
+hipError_t dispatch_expm_variants(int D, const DevProblem &P, const DevBatch &B, const grape::FactorTab &F,
+                                  hipStream_t st) {
+    return dispatch_dim(D, [&](auto d) { return grape_host::launch_expm_variants<decltype(d)::value>(P, B, F, st); });
 }
 hipError_t dispatch_expm_table(int D, const DevProblem &P, const DevBatch &B, hipStream_t st) {
     return dispatch_dim(D, [&](auto d) { return grape_host::launch_expm_table<decltype(d)::value>(P, B, st); });
@@ -187,6 +189,10 @@ struct grape_plan {
     cd *d_opsT = nullptr;
     Term *d_h0 = nullptr, *d_tgt = nullptr, *d_err = nullptr;
     int *d_err_off = nullptr;
+    // product coefficients (grape.h GRAPE_OP_FACTOR): the factor slots of the H0 and error terms, an argument
+    // of the product kernels (grape_prod.hpp); FT.h0 is null for a plan without factor terms
+    grape::FactorTab FT{};
+    Term *d_fac_h0 = nullptr, *d_fac_err = nullptr;
     double *d_W = nullptr;
     cd *d_E = nullptr, *d_Q = nullptr, *d_Mc = nullptr, *d_Carry = nullptr, *d_Ub = nullptr, *d_Me = nullptr;
     grape::VSpec *d_vs = nullptr;
@@ -350,8 +356,23 @@ static void free_plan(grape_plan *p) {
 }
 
 static int validate_terms(const grape_term *t, int n, int n_ops, int np, int na, bool target, const char *what) {
+    int nfac = 0;  // factor terms on the current operator term
     for (int k = 0; k < n; ++k) {
-        if (t[k].op < 0 || t[k].op >= n_ops) return fail(GRAPE_ERR_INVALID, std::string(what) + ": op out of range");
+        const bool factor = t[k].op == GRAPE_OP_FACTOR;
+        if (factor) {  // product coefficients: a real scalar on the closest preceding operator term of this list
+            if (target) return fail(GRAPE_ERR_INVALID, std::string(what) + ": factor terms are not allowed in target terms");
+            if (k == 0)
+                return fail(GRAPE_ERR_INVALID, std::string(what) + ": a factor term must follow an operator term of its list");
+            if (++nfac > GRAPE_MAX_FACTORS)
+                return fail(GRAPE_ERR_INVALID, std::string(what) + ": more than GRAPE_MAX_FACTORS factor terms on one operator term");
+            if (t[k].func < GRAPE_FN_ONE || t[k].func > GRAPE_FN_SIN)
+                return fail(GRAPE_ERR_INVALID, std::string(what) + ": a factor term's func must be ONE, LINEAR, COS or SIN");
+            if (t[k].scale_im != 0.0)
+                return fail(GRAPE_ERR_INVALID, std::string(what) + ": a factor term's scale must be real (scale_im = 0)");
+        } else {
+            nfac = 0;
+        }
+        if (!factor && (t[k].op < 0 || t[k].op >= n_ops)) return fail(GRAPE_ERR_INVALID, std::string(what) + ": op out of range");
         if (t[k].var < 0 || t[k].var > 3) return fail(GRAPE_ERR_INVALID, std::string(what) + ": bad var");
         if (t[k].func < 0 || t[k].func > 4) return fail(GRAPE_ERR_INVALID, std::string(what) + ": bad func");
         if (t[k].var == 1 && (t[k].index < 0 || t[k].index >= np))
@@ -364,6 +385,63 @@ static int validate_terms(const grape_term *t, int n, int n_ops, int np, int na,
             return fail(GRAPE_ERR_INVALID, std::string(what) + ": cis coefficients only in target terms");
     }
     return GRAPE_OK;
+}
+
+// Product coefficients (grape.h GRAPE_OP_FACTOR).  A validated descriptor split once into the plain
+// descriptor every other piece of host logic sees -- operator terms only, err_term_offsets re-based, so
+// that nothing ever indexes ops[-1] -- and the factor slots of its H0 and error terms
+// (grape_kernels.hpp FactorTab: kMaxFactors slots per operator term, op = 1 live, 0 empty).  A descriptor
+// without factor terms is passed through untouched (plain = *desc, the caller's own pointers).
+struct FactorSplit {
+    bool any = false;
+    bool reads_xadd = false, reads_tstep = false;  // some factor reads x_add / the step index
+    grape_desc plain{};
+    std::vector<grape_term> h0, err, fac_h0, fac_err;
+    std::vector<int32_t> err_off;
+};
+static void split_list(const grape_term *t, int n, std::vector<grape_term> &ops, std::vector<grape_term> &fac,
+                       FactorSplit &fs) {
+    int slot = 0;
+    for (int k = 0; k < n; ++k) {
+        if (t[k].op != GRAPE_OP_FACTOR) {
+            ops.push_back(t[k]);
+            grape_term empty{};  // op = 0: an empty slot
+            fac.insert(fac.end(), (size_t)GRAPE_MAX_FACTORS, empty);
+            slot = 0;
+        } else if (!ops.empty() && slot < GRAPE_MAX_FACTORS) {
+            grape_term f = t[k];
+            f.op = 1;
+            fac[fac.size() - (size_t)GRAPE_MAX_FACTORS + (size_t)slot++] = f;
+            fs.any = true;
+            fs.reads_xadd = fs.reads_xadd || f.var == GRAPE_VAR_XADD;
+            fs.reads_tstep = fs.reads_tstep || f.var == GRAPE_VAR_TSTEP;
+        }
+    }
+}
+static void split_factors(const grape_desc *desc, FactorSplit &fs) {
+    fs.plain = *desc;
+    if ((desc->reserved[0] & GRAPE_DESC_HOST_TABLES) || !desc->h0_terms) return;
+    split_list(desc->h0_terms, desc->n_h0_terms, fs.h0, fs.fac_h0, fs);
+    if (desc->nerr > 0 && desc->err_term_offsets && desc->err_terms) {
+        fs.err_off.push_back(0);
+        for (int e = 0; e < desc->nerr; ++e) {
+            const int a = desc->err_term_offsets[e], b = desc->err_term_offsets[e + 1];
+            split_list(desc->err_terms + a, b - a, fs.err, fs.fac_err, fs);
+            fs.err_off.push_back((int32_t)fs.err.size());
+        }
+    }
+    if (!fs.any) return;  // the caller's descriptor as it is
+    fs.plain.h0_terms = fs.h0.data();
+    fs.plain.n_h0_terms = (int32_t)fs.h0.size();
+    if (!fs.err_off.empty()) {
+        fs.plain.err_terms = fs.err.data();
+        fs.plain.err_term_offsets = fs.err_off.data();
+    }
+    // the stored pipeline only: no lane matrices, chains, chunk walks (so no gauge search, pair, merged or
+    // wide passes) and no one-workgroup kernel -- those build generators from the plain term lists
+    fs.plain.reserved[1] |= GRAPE_OPT_NO_LANE | GRAPE_OPT_NO_CHAIN | GRAPE_OPT_NO_WALK | GRAPE_OPT_NO_GAUGE |
+                            GRAPE_OPT_NO_PAIR | GRAPE_OPT_NO_MERGE | GRAPE_OPT_NO_RANK1 | GRAPE_OPT_NO_WIDE |
+                            GRAPE_OPT_NO_EVAL1 | GRAPE_OPT_NO_TWIN;
 }
 
 // The fused engines take C_k^-1 = C_k^dagger for the chain C_k of the NOMINAL propagators
@@ -905,7 +983,11 @@ extern "C" int grape_symmetry_basis(const grape_desc *desc, double *V, int *bloc
         return fail(GRAPE_ERR_INVALID, "grape_symmetry_basis: operator-basis descriptor with 1 <= ndim <= 12");
     const int D = desc->ndim;
     for (int t = 0; t < desc->n_h0_terms; ++t)
-        if (desc->h0_terms[t].op < 0 || desc->h0_terms[t].op >= desc->n_ops) return fail(GRAPE_ERR_INVALID, "bad op index");
+        if (desc->h0_terms[t].op != GRAPE_OP_FACTOR && (desc->h0_terms[t].op < 0 || desc->h0_terms[t].op >= desc->n_ops))
+            return fail(GRAPE_ERR_INVALID, "bad op index");
+    FactorSplit fs;  // factor terms carry no operator: the operator terms alone span the algebra
+    split_factors(desc, fs);
+    desc = &fs.plain;
     const grape_sym::Split sp = grape_sym::symmetry_split(D, used_operators(desc));
     for (size_t t = 0; t < sp.V.size(); ++t) {
         V[2 * t] = sp.V[t].real();
@@ -1209,10 +1291,34 @@ static int validate_desc(const grape_desc *desc, int *n_err_terms) {
                 return fail(GRAPE_ERR_INVALID, "each error source needs at least one term");
         if (desc->err_term_offsets[0] != 0) return fail(GRAPE_ERR_INVALID, "err_term_offsets[0] must be 0");
         *n_err_terms = desc->err_term_offsets[desc->nerr];
-        if ((rc = validate_terms(desc->err_terms, *n_err_terms, desc->n_ops, desc->nparam, desc->nadd, false,
-                                 "error source")))
-            return rc;
+        for (int e = 0; e < desc->nerr; ++e)  // per source: a factor term never starts a source's range
+            if ((rc = validate_terms(desc->err_terms + desc->err_term_offsets[e],
+                                     desc->err_term_offsets[e + 1] - desc->err_term_offsets[e], desc->n_ops, desc->nparam,
+                                     desc->nadd, false, "error source")))
+                return rc;
     }
+    if (!tables && D > GRAPE_MAX_SMALL_DIM) {  // product coefficients: the small engine's stored pipeline only
+        bool any = false;
+        for (int k = 0; k < desc->n_h0_terms; ++k) any = any || desc->h0_terms[k].op == GRAPE_OP_FACTOR;
+        for (int k = 0; k < *n_err_terms; ++k) any = any || desc->err_terms[k].op == GRAPE_OP_FACTOR;
+        if (any)
+            return fail(GRAPE_ERR_UNSUPPORTED, "product coefficients (factor terms) are served up to GRAPE_MAX_SMALL_DIM "
+                                               "levels; the dense and tiled engines do not take them");
+    }
+    return GRAPE_OK;
+}
+
+// the factor slots on the plan's device
+static int upload_factors(grape_plan *p, const FactorSplit &fs) {
+    if (!fs.any) return GRAPE_OK;
+    if (p->mem.alloc(&p->d_fac_h0, fs.fac_h0.size()) != hipSuccess || p->mem.alloc(&p->d_fac_err, fs.fac_err.size()) != hipSuccess)
+        return fail(GRAPE_ERR_ALLOC, "device allocation failed (product factors)");
+    if (hipMemcpy(p->d_fac_h0, fs.fac_h0.data(), fs.fac_h0.size() * sizeof(Term), hipMemcpyHostToDevice) != hipSuccess ||
+        (!fs.fac_err.empty() &&
+         hipMemcpy(p->d_fac_err, fs.fac_err.data(), fs.fac_err.size() * sizeof(Term), hipMemcpyHostToDevice) != hipSuccess))
+        return fail(GRAPE_ERR_HIP, "upload failed (product factors)");
+    p->FT.h0 = p->d_fac_h0;
+    p->FT.err = p->d_fac_err;
     return GRAPE_OK;
 }
 
@@ -1892,13 +1998,19 @@ int grape_device_count(void) {
     return n;
 }
 
-int grape_plan_create(const grape_desc *desc, int device, grape_plan **out) {
-    if (!desc || !out) return fail(GRAPE_ERR_INVALID, "null argument");
+int grape_plan_create(const grape_desc *full, int device, grape_plan **out) {
+    if (!full || !out) return fail(GRAPE_ERR_INVALID, "null argument");
     *out = nullptr;
     int n_err_terms = 0;
     Route rt;
-    if (int rc = validate_desc(desc, &n_err_terms)) return rc;
+    if (int rc = validate_desc(full, &n_err_terms)) return rc;
+    // product coefficients: everything below sees the plain descriptor (operator terms only)
+    FactorSplit fs;
+    split_factors(full, fs);
+    const grape_desc *desc = &fs.plain;
+    if (fs.any) n_err_terms = (int)fs.err.size();
     if (int rc = choose_route(desc, n_err_terms, rt)) return rc;
+    if (fs.reads_xadd) rt.xadd_dep = true;  // a factor on x_add: the x_add variants exist
     const ProjectorSetup ps = setup_projector(desc);
     if (!(ps.trP > 0)) return fail(GRAPE_ERR_INVALID, "projector trace must be positive");
     int ndev = 0;
@@ -1907,6 +2019,7 @@ int grape_plan_create(const grape_desc *desc, int device, grape_plan **out) {
 
     grape_plan *p = new grape_plan();
     int rc = open_plan(p, desc, device, rt);
+    if (fs.reads_tstep) p->uses_tstep = true;
     if (!rc && desc->ndim > GRAPE_MAX_DENSE_DIM) {
         rc = create_tiled(desc, p, ps);
     } else if (!rc && desc->ndim > GRAPE_MAX_SMALL_DIM && !rt.tables && !rt.pivot) {
@@ -1914,6 +2027,7 @@ int grape_plan_create(const grape_desc *desc, int device, grape_plan **out) {
     } else if (!rc) {
         PlanBuild b{desc, p, rt, ps, n_err_terms};
         rc = create_small(b);
+        if (!rc) rc = upload_factors(p, fs);
     }
     if (rc) {  // (the message is set; the plan's pool returns whatever was allocated so far)
         free_plan(p);
@@ -2236,7 +2350,7 @@ static int enqueue(grape_plan *p, int nb, const double *d_x, double *d_F, double
             }
             if (!fork || pair) {
                 for (int cl = 0; cl < p->ncls; ++cl) {
-                    const hipError_t e = dispatch_sector_stage(p->Ps[cl].D, s, p->Ps[cl], Bc[cl], st, mk);
+                    const hipError_t e = dispatch_sector_stage(p->Ps[cl].D, s, p->Ps[cl], Bc[cl], p->FT, st, mk);
                     if (e != hipSuccess) return e;
                 }
                 return hipSuccess;
@@ -2244,9 +2358,9 @@ static int enqueue(grape_plan *p, int nb, const double *d_x, double *d_F, double
             hipEvent_t evf = p->ev_fork, evj = p->ev_join;
             hipError_t e = hipEventRecord(evf, st);
             if (e == hipSuccess) e = hipStreamWaitEvent(p->aux_stream, evf, 0);
-            if (e == hipSuccess) e = dispatch_sector_stage(p->Ps[0].D, s, p->Ps[0], Bc[0], st, mk);
+            if (e == hipSuccess) e = dispatch_sector_stage(p->Ps[0].D, s, p->Ps[0], Bc[0], p->FT, st, mk);
             p->cur_stream = p->aux_stream;
-            if (e == hipSuccess) e = dispatch_sector_stage(p->Ps[1].D, s, p->Ps[1], Bc[1], p->aux_stream, mk);
+            if (e == hipSuccess) e = dispatch_sector_stage(p->Ps[1].D, s, p->Ps[1], Bc[1], p->FT, p->aux_stream, mk);
             p->cur_stream = st;
             if (e == hipSuccess) e = hipEventRecord(evj, p->aux_stream);
             if (e == hipSuccess) e = hipStreamWaitEvent(st, evj, 0);
@@ -2312,7 +2426,7 @@ static int enqueue(grape_plan *p, int nb, const double *d_x, double *d_F, double
         B.Htab = p->d_Htab;
         B.U0tab = p->d_U0tab;
     }
-    HIPCHECK(dispatch_pipeline(P.D, P, B, st, mk));
+    HIPCHECK(dispatch_pipeline(P.D, P, B, p->FT, st, mk));
     return GRAPE_OK;
 }
 
@@ -2748,7 +2862,7 @@ static int ud_propagators_dev(grape_plan *p, const double *d_x, int nv, const cd
         Bu.Htab = d_Htab;
         HIPCHECK(dispatch_expm_table(P0.D, Pu, Bu, st));
     } else {
-        HIPCHECK(dispatch_expm_variants(P0.D, Pu, Bu, st));
+        HIPCHECK(dispatch_expm_variants(P0.D, Pu, Bu, p->FT, st));
     }
     return GRAPE_OK;
 }
@@ -2803,7 +2917,7 @@ static int ud_interaction(grape_plan *p, const double *x, const double *H0tab, c
         HIPCHECK(hipMemcpyAsync(dO, Oerr, n * sizeof(cd), hipMemcpyHostToDevice, p->stream));
         HIPCHECK(grape_unitary::launch_interaction_table(p->P, dO, p->ud_C, Ci, p->ud_out, p->ud_gscr, p->stream));
     } else {
-        HIPCHECK(grape_unitary::launch_interaction(p->P, p->d_x, p->ud_C, Ci, p->ud_out, p->ud_gscr, p->stream));
+        HIPCHECK(grape_unitary::launch_interaction(p->P, p->d_x, p->ud_C, Ci, p->ud_out, p->ud_gscr, p->FT.err, p->stream));
     }
     return GRAPE_OK;
 }

@@ -54,6 +54,17 @@ struct VSpec {
     double errval;
 };
 
+// Product coefficients (grape.h GRAPE_OP_FACTOR): the factor terms of every operator term of P.h0 and of
+// P.err, kMaxFactors slots per operator term in the lists' order.  A slot's op is 1 when it holds a factor
+// and 0 when it is empty; its value scale * f(a v + b) is real.  Plans without factor terms have h0 = null.
+// An argument of its own of the product kernels (grape_prod.hpp), not a field of DevProblem: every kernel
+// takes that by value.
+constexpr int kMaxFactors = 2;  // GRAPE_MAX_FACTORS
+struct FactorTab {
+    const Term *h0;   // [n_h0][kMaxFactors]
+    const Term *err;  // [err_off[ne]][kMaxFactors]
+};
+
 // Everything a kernel needs to know about the problem (passed by value).
 struct DevProblem {
     int D, Nt, np, na, ne, nx;
@@ -347,8 +358,10 @@ __device__ __forceinline__ void park(Group<D> &G, cd *slot_row, const cd (&a)[D]
 #ifndef GRAPE_EXPM_WAVES_D9
 #define GRAPE_EXPM_WAVES_D9 3   // waves per SIMD requested for d <= 9 (register budget 512/w)
 #endif
-template <int D, bool ERR>
-__global__ __launch_bounds__(64, (D <= 9 ? GRAPE_EXPM_WAVES_D9 : 2)) void k_expm(DevProblem P, DevBatch B) {
+// The body of k_expm for any builder of the generator's column (ItemBuilder here; the product builder of
+// grape_prod.hpp): make(xk, xadd, i, nt1, vs, valid, sector) returns the item's builder.
+template <int D, bool ERR, class Make>
+__device__ __forceinline__ void expm_item_body(const DevProblem &P, const DevBatch &B, Make make) {
     constexpr int RING = ERR ? 2 : 3;  // LDS read ring of the products (mm_tile_ring)
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     cd *lds = reinterpret_cast<cd *>(smem_raw);
@@ -361,8 +374,7 @@ __global__ __launch_bounds__(64, (D <= 9 ? GRAPE_EXPM_WAVES_D9 : 2)) void k_expm
     split_item(gidc, nitems, P.nv, P.Nt, b, k, v);
     const int ns = P.nsec > 1 ? P.nsec : 1, bx = b / ns;  // sectors: evaluation bx, sector b - bx * ns
     const double *xb = B.x + (size_t)bx * P.nx;
-    const ItemBuilder<D, ERR> rebuild(&P, xb + (size_t)k * P.np, xb + (size_t)P.np * P.Nt, G.i, k + 1, P.vs[v],
-                                      valid, b - bx * ns);
+    const auto rebuild = make(xb + (size_t)k * P.np, xb + (size_t)P.np * P.Nt, G.i, k + 1, P.vs[v], valid, b - bx * ns);
     cd a[D], x[D];
     rebuild(a);
     int s = 0;
@@ -378,6 +390,11 @@ __global__ __launch_bounds__(64, (D <= 9 ? GRAPE_EXPM_WAVES_D9 : 2)) void k_expm
 #pragma unroll
         for (int j = 0; j < D; ++j) col[j * D] = x[j];
     }
+}
+template <int D, bool ERR>
+__global__ __launch_bounds__(64, (D <= 9 ? GRAPE_EXPM_WAVES_D9 : 2)) void k_expm(DevProblem P, DevBatch B) {
+    expm_item_body<D, ERR>(P, B, [&](const double *xk, const double *xadd, int i, int nt1, const VSpec &vs, bool valid,
+                                     int sector) { return ItemBuilder<D, ERR>(&P, xk, xadd, i, nt1, vs, valid, sector); });
 }
 
 // Closure mode: column i of A = -i dt H for item gid from the host-evaluated table
@@ -866,8 +883,9 @@ __global__ __launch_bounds__(64, (D <= 9 ? 4 : 2)) void k_grad(DevProblem P, Dev
 // the variant's propagator E' = exp(-i dt H(x + eps e_u)) is computed and
 // contracted on the spot -- it never goes to memory.  Pade m > 5 items are
 // parked (A to a slot) for k_grad_high.
-template <int D>
-__global__ __launch_bounds__(64, (D <= 9 ? GRAPE_EXPM_GRAD_WAVES : 2)) void k_expm_grad(DevProblem P, DevBatch B) {
+// (the body for any builder of the generator's column, as expm_item_body)
+template <int D, class Make>
+__device__ __forceinline__ void expm_grad_item_body(const DevProblem &P, const DevBatch &B, Make make) {
     constexpr int RING = 2;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     cd *lds = reinterpret_cast<cd *>(smem_raw);
@@ -882,8 +900,8 @@ __global__ __launch_bounds__(64, (D <= 9 ? GRAPE_EXPM_GRAD_WAVES : 2)) void k_ex
     split_item(gidc, nitems, nvg, P.Nt, b, k, u);
     const int ns = P.nsec > 1 ? P.nsec : 1, bx = b / ns;
     const double *xb = B.x + (size_t)bx * P.nx;
-    const ItemBuilder<D, false> rebuild(&P, xb + (size_t)k * P.np, xb + (size_t)P.np * P.Nt, G.i, k + 1,
-                                        P.vs[P.off_dx + u], valid, b - bx * ns);
+    const auto rebuild = make(xb + (size_t)k * P.np, xb + (size_t)P.np * P.Nt, G.i, k + 1, P.vs[P.off_dx + u], valid,
+                              b - bx * ns);
     cd a[D], x[D];
     rebuild(a);
     int s = 0;
@@ -896,6 +914,11 @@ __global__ __launch_bounds__(64, (D <= 9 ? GRAPE_EXPM_GRAD_WAVES : 2)) void k_ex
     cd z[D], e0[D];
     grad_kernel_col<D, RING>(G, P, B, b, k, valid, z, e0);  // e0: column i of E_k
     grad_store<D>(G, P, B, b, k, u, z, x, e0, valid);
+}
+template <int D>
+__global__ __launch_bounds__(64, (D <= 9 ? GRAPE_EXPM_GRAD_WAVES : 2)) void k_expm_grad(DevProblem P, DevBatch B) {
+    expm_grad_item_body<D>(P, B, [&](const double *xk, const double *xadd, int i, int nt1, const VSpec &vs, bool valid,
+                                     int sector) { return ItemBuilder<D, false>(&P, xk, xadd, i, nt1, vs, valid, sector); });
 }
 
 // Parked k_expm_grad items: Pade m = 7/9/13, then the same contraction.

@@ -137,6 +137,14 @@ void launch_err_scan(const DevProblem &P, const DevBatch &B, hipStream_t st) {
                            errscan_lds<D>(kScanWide), st, P, B);
 }
 
+// Product coefficients (grape_prod.hpp): plans with factor terms (F.h0 set) run k_expm_prod / k_expm_grad_prod
+// wherever the sequences below launch k_expm / k_expm_grad.  Defined and instantiated per dimension in
+// grape_prod_inst.hip; the launch geometry is that of the plain kernels.
+template <int D>
+hipError_t launch_expm_prod(bool err, const DevProblem &P, const DevBatch &B, const grape::FactorTab &F, hipStream_t st);
+template <int D>
+hipError_t launch_expm_grad_prod(const DevProblem &P, const DevBatch &B, const grape::FactorTab &F, hipStream_t st);
+
 // ---------------------------------------------------------------------------
 // dispatch helpers over the compile-time dimension
 // ---------------------------------------------------------------------------
@@ -150,8 +158,10 @@ struct KMark {
 };
 
 template <int D>
-hipError_t launch_pipeline(const DevProblem &P, const DevBatch &B, hipStream_t st, const KMark &mark) {
+hipError_t launch_pipeline(const DevProblem &P, const DevBatch &B, const grape::FactorTab &F, hipStream_t st,
+                           const KMark &mark) {
     constexpr int GPW = grape::Geo<D>::GPW;
+    const bool prod = F.h0 != nullptr;  // factor terms: the product builder's kernels
     const long nexp = (long)B.nb * P.Nt * P.nv;
     // closure mode (grape_fidelity_grad_tables): every variant comes from the host H table
     const bool table = B.Htab != nullptr;
@@ -160,6 +170,8 @@ hipError_t launch_pipeline(const DevProblem &P, const DevBatch &B, hipStream_t s
     if (table)
         hipLaunchKernelGGL(grape::k_expm_table<D>, dim3((unsigned)((nexp + GPW - 1) / GPW)), dim3(64),
                            expm_lean_lds<D>(), st, P, B);
+    else if (prod)
+        (void)launch_expm_prod<D>(!fused, P, B, F, st);
     else if (use_lane<D>(P, B))
         fused ? launch_expm_lane<D, false>(P, B, st) : launch_expm_lane<D, true>(P, B, st);
     else if (!fused)
@@ -184,8 +196,11 @@ hipError_t launch_pipeline(const DevProblem &P, const DevBatch &B, hipStream_t s
         const int nvg = P.np + (P.xadd_dep ? P.na : 0);
         const long ng = (long)B.nb * P.Nt * nvg;
         mark(GRAPE_KERNEL_EXPM_GRAD, 0);
-        hipLaunchKernelGGL(grape::k_expm_grad<D>, dim3((unsigned)((ng + GPW - 1) / GPW)), dim3(64),
-                           expm_lean_lds<D>(), st, P, B);
+        if (prod)
+            (void)launch_expm_grad_prod<D>(P, B, F, st);
+        else
+            hipLaunchKernelGGL(grape::k_expm_grad<D>, dim3((unsigned)((ng + GPW - 1) / GPW)), dim3(64),
+                               expm_lean_lds<D>(), st, P, B);
         mark(GRAPE_KERNEL_EXPM_GRAD, 1);
         mark(GRAPE_KERNEL_GRAD_HIGH, 0);
         hipLaunchKernelGGL(grape::k_grad_high<D>, dim3(64), dim3(64), expm_lds<D>(), st, P, B);
@@ -235,9 +250,10 @@ hipError_t launch_pipeline(const DevProblem &P, const DevBatch &B, hipStream_t s
 // head (F_d2err, the blocks of M_e).  Stage 2 (error sources): M'_{c,e} (k_sec_mc_err) and
 // the F_d2err_dx walks.  Finally launch_sector_reduce sums the sector terms.
 template <int D>
-hipError_t launch_sector_stage(int stage, const DevProblem &P, const DevBatch &B, hipStream_t st,
-                               const KMark &mark) {
+hipError_t launch_sector_stage(int stage, const DevProblem &P, const DevBatch &B, const grape::FactorTab &F,
+                               hipStream_t st, const KMark &mark) {
     constexpr int GPW = grape::Geo<D>::GPW;
+    const bool prod = F.h0 != nullptr;  // factor terms (never a walk, lane or chain class: the plan's option bits)
     if constexpr (D >= 2 && D <= grape::kWalkMaxD) {
         if (P.walk) {  // chunk walks (grape_walk.hpp): no E / Q intermediates
             if (stage == 0) {
@@ -303,7 +319,9 @@ hipError_t launch_sector_stage(int stage, const DevProblem &P, const DevBatch &B
             }
         }
         mark(GRAPE_KERNEL_EXPM, 0);
-        if (use_lane<D>(P, B))
+        if (prod)
+            (void)launch_expm_prod<D>(P.ne > 0, P, B, F, st);
+        else if (use_lane<D>(P, B))
             P.ne > 0 ? launch_expm_lane<D, true>(P, B, st) : launch_expm_lane<D, false>(P, B, st);
         else if (P.ne > 0)
             hipLaunchKernelGGL((grape::k_expm<D, true>), dim3((unsigned)((nexp + GPW - 1) / GPW)), dim3(64),
@@ -339,8 +357,11 @@ hipError_t launch_sector_stage(int stage, const DevProblem &P, const DevBatch &B
         }
         const long ng = (long)B.nb * P.Nt * P.nvg;
         mark(GRAPE_KERNEL_EXPM_GRAD, 0);
-        hipLaunchKernelGGL(grape::k_expm_grad<D>, dim3((unsigned)((ng + GPW - 1) / GPW)), dim3(64),
-                           expm_lean_lds<D>(), st, P, B);
+        if (prod)
+            (void)launch_expm_grad_prod<D>(P, B, F, st);
+        else
+            hipLaunchKernelGGL(grape::k_expm_grad<D>, dim3((unsigned)((ng + GPW - 1) / GPW)), dim3(64),
+                               expm_lean_lds<D>(), st, P, B);
         mark(GRAPE_KERNEL_EXPM_GRAD, 1);
         mark(GRAPE_KERNEL_GRAD_HIGH, 0);
         hipLaunchKernelGGL(grape::k_grad_high<D>, dim3(64), dim3(64), expm_lds<D>(), st, P, B);
@@ -397,10 +418,12 @@ hipError_t launch_expm_raw(const cd *A, cd *E, int n, int *ovf, int *ovf_count, 
 // as given): grape_unitary_derivs' propagator table.  ERR selects the builder with
 // error terms.
 template <int D>
-hipError_t launch_expm_variants(const DevProblem &P, const DevBatch &B, hipStream_t st) {
+hipError_t launch_expm_variants(const DevProblem &P, const DevBatch &B, const grape::FactorTab &F, hipStream_t st) {
     constexpr int GPW = grape::Geo<D>::GPW;
     const long nexp = (long)B.nb * P.Nt * P.nv;
-    if (P.ne > 0)
+    if (F.h0)
+        (void)launch_expm_prod<D>(P.ne > 0, P, B, F, st);
+    else if (P.ne > 0)
         hipLaunchKernelGGL((grape::k_expm<D, true>), dim3((unsigned)((nexp + GPW - 1) / GPW)), dim3(64),
                            expm_lean_lds<D>(), st, P, B);
     else
@@ -455,14 +478,16 @@ hipError_t set_lds_limits() {
                                                     const DevBatch &, hipStream_t);
 
 #define GRAPE_DECLARE_DIM(d, EXT)                                                                          \
-    EXT template hipError_t launch_pipeline<d>(const DevProblem &, const DevBatch &, hipStream_t, const KMark &); \
-    EXT template hipError_t launch_sector_stage<d>(int, const DevProblem &, const DevBatch &, hipStream_t,     \
-                                                   const KMark &);                                            \
+    EXT template hipError_t launch_pipeline<d>(const DevProblem &, const DevBatch &, const grape::FactorTab &, \
+                                               hipStream_t, const KMark &);                                   \
+    EXT template hipError_t launch_sector_stage<d>(int, const DevProblem &, const DevBatch &,                \
+                                                   const grape::FactorTab &, hipStream_t, const KMark &);     \
     EXT template hipError_t launch_sector_reduce<d>(const DevProblem &, const DevBatch &, const grape::SecParts &, \
                                                     int, hipStream_t, const KMark &);                         \
     EXT template hipError_t launch_expm_raw<d>(const cd *, cd *, int, int *, int *, int *, int *, hipStream_t);  \
     EXT template hipError_t set_lds_limits<d>();                                                          \
-    EXT template hipError_t launch_expm_variants<d>(const DevProblem &, const DevBatch &, hipStream_t);     \
+    EXT template hipError_t launch_expm_variants<d>(const DevProblem &, const DevBatch &, const grape::FactorTab &, \
+                                                    hipStream_t);                                          \
     EXT template hipError_t launch_expm_table<d>(const DevProblem &, const DevBatch &, hipStream_t);
 
 }  // namespace grape_host

@@ -323,7 +323,7 @@ __global__ __launch_bounds__(BLOCK) void k_u_reduce(UProblem P, const cd *C, con
 
 // O_{k,e} = C_{k-1}^-1 (Herror_e / eps) C_{k-1}: items (k, e); C^-1 = C^dagger unless Ci is given
 __global__ __launch_bounds__(BLOCK) void k_u_interaction(grape::DevProblem P, const double *x, const cd *C,
-                                                         const cd *Ci, cd *O, cd *gscr) {
+                                                         const cd *Ci, cd *O, cd *gscr, const grape::Term *fac) {
     __shared__ cd lds[kTiles * kMaxD * kMaxD];
     const int D = P.D, DD = D * D, t0 = threadIdx.x;
     cd *sC = tiles(lds, gscr, D), *sH = sC + DD, *sT = sH + DD, *sCi = sT + DD;
@@ -344,7 +344,14 @@ __global__ __launch_bounds__(BLOCK) void k_u_interaction(grape::DevProblem P, co
             cd h{0.0, 0.0};
             for (int q = P.err_off[e]; q < P.err_off[e + 1]; ++q) {
                 const grape::Term tm = P.err[q];
-                h = u_add(h, u_mul(grape::term_coef(tm, k + 1, xk, xadd, none), P.ops[(size_t)tm.op * DD + t]));
+                cd c = grape::term_coef(tm, k + 1, xk, xadd, none);
+                if (fac) {  // product coefficients: the term's factor slots (real values; op = 0: empty)
+                    for (int j = 0; j < grape::kMaxFactors; ++j) {
+                        const grape::Term f = fac[(size_t)q * grape::kMaxFactors + j];
+                        if (f.op) c = u_scale(grape::term_coef(f, k + 1, xk, xadd, none).re, c);
+                    }
+                }
+                h = u_add(h, u_mul(c, P.ops[(size_t)tm.op * DD + t]));
             }
             sH[t] = u_scale(1.0 / P.eps, u_scale(P.eps, h));
         }
@@ -636,9 +643,9 @@ hipError_t launch_inverse(const UProblem &P, const cd *C, cd *Ci, int *status, h
 }
 
 hipError_t launch_interaction(const grape::DevProblem &P, const double *x, const cd *C, const cd *Ci, cd *O,
-                              cd *gscr, hipStream_t st) {
+                              cd *gscr, const grape::Term *fac, hipStream_t st) {
     hipLaunchKernelGGL(k_u_interaction, dim3(grid_for(P.D, (long)P.Nt * P.ne)), dim3(BLOCK), 0, st, P, x, C, Ci, O,
-                       gscr);
+                       gscr, fac);
     return hipGetLastError();
 }
 

@@ -50,9 +50,10 @@ hipError_t launch_inverse(const UProblem &P, const cd *C, cd *Ci, int *status, h
 hipError_t launch_chain(const UProblem &P, const cd *E, cd *C, hipStream_t st);
 // O[:, :, k, e] = C_{k-1}^-1 (Herror_e(k, eps) / eps) C_{k-1}, column-major (d, d, Nt, ne)
 // (UnitaryCalculations.jl:180-204; C^-1 = Ci when given, else C^dagger); x is the plan's device
-// copy of the control vector
+// copy of the control vector; fac: the error terms' factor slots (grape_kernels.hpp FactorTab::err) of a plan
+// with product coefficients, else null
 hipError_t launch_interaction(const grape::DevProblem &P, const double *x, const cd *C, const cd *Ci, cd *O,
-                              cd *gscr, hipStream_t st);
+                              cd *gscr, const grape::Term *fac, hipStream_t st);
 // The same from host-evaluated closures (closure fallback): Oerr [Nt][ne][D][D] column-major
 // holds (1/eps) Herror_e(k, x_k, x_add, eps) as the reference forms it
 hipError_t launch_interaction_table(const grape::DevProblem &P, const cd *Oerr, const cd *C, const cd *Ci, cd *O,

@@ -7,6 +7,10 @@ sum of fixed operators times scalar coefficients (see ``include/grape.h``):
 
     H(nt, x, x_add) = sum_t scale_t * f_t(a_t * v_t + b_t) * OP_t
 
+A term of H0 or of an error source may carry up to two real scalar ``Factor``s that multiply its
+coefficient (``GRAPE_OP_FACTOR``): an amplitude x phase drive ``Omega_k (cos phi_k Hc + sin phi_k Hs)``,
+an envelope ``w(k) x_k``, a global scale ``x_add[q] x_k``.
+
 Each descriptor is ALSO a callable with the reference signature, so it can be
 handed to anything that expects the closure (including the CPU oracle).
 """
@@ -23,9 +27,60 @@ VAR_ONE, VAR_X, VAR_XADD, VAR_TSTEP = 0, 1, 2, 3
 FN_ONE, FN_LINEAR, FN_COS, FN_SIN, FN_CIS = 0, 1, 2, 3, 4
 
 
+OP_FACTOR = -1    # GRAPE_OP_FACTOR: a grape_term that carries no operator (a Factor)
+MAX_FACTORS = 2   # GRAPE_MAX_FACTORS
+
+
+def _value(var, index, func, a, b, nt, x, x_add):
+    """f(a * v + b) of grape_var / grape_func."""
+    if var == VAR_ONE:
+        v = 1.0
+    elif var == VAR_X:
+        v = float(x[index])
+    elif var == VAR_XADD:
+        v = float(x_add[index])
+    elif var == VAR_TSTEP:
+        v = float(nt)
+    else:
+        raise ValueError(f"bad var {var}")
+    t = a * v + b
+    if func == FN_ONE:
+        return 1.0
+    if func == FN_LINEAR:
+        return t
+    if func == FN_COS:
+        return np.cos(t)
+    if func == FN_SIN:
+        return np.sin(t)
+    if func == FN_CIS:
+        return complex(np.cos(t), np.sin(t))
+    raise ValueError(f"bad func {func}")
+
+
+@dataclass(frozen=True)
+class Factor:
+    """A real scalar ``scale * f(a * v + b)`` that multiplies the coefficient of the Term holding it
+    (a grape_term with op = GRAPE_OP_FACTOR)."""
+    var: int
+    index: int = 0
+    func: int = FN_LINEAR
+    a: float = 1.0
+    b: float = 0.0
+    scale: float = 1.0
+
+    def __post_init__(self):
+        if self.func not in (FN_ONE, FN_LINEAR, FN_COS, FN_SIN):
+            raise ValueError("a Factor's func must be FN_ONE, FN_LINEAR, FN_COS or FN_SIN")
+        if complex(self.scale).imag != 0.0:
+            raise ValueError("a Factor's scale must be real")
+
+    def value(self, nt, x, x_add):
+        return float(complex(self.scale).real) * _value(self.var, self.index, self.func, self.a, self.b, nt, x, x_add)
+
+
 @dataclass(frozen=True)
 class Term:
-    """One coefficient * operator term (grape_term)."""
+    """One coefficient * operator term (grape_term), with up to MAX_FACTORS scalar factors."""
     op: np.ndarray          # (d, d) complex
     var: int = VAR_ONE
     index: int = 0
@@ -33,35 +88,27 @@ class Term:
     a: float = 1.0
     b: float = 0.0
     scale: complex = 1.0
+    factors: Tuple[Factor, ...] = ()
+
+    def __post_init__(self):
+        object.__setattr__(self, "factors", tuple(self.factors))
+        if len(self.factors) > MAX_FACTORS:
+            raise ValueError(f"a Term takes at most {MAX_FACTORS} factors")
 
     def coefficient(self, nt, x, x_add):
-        if self.var == VAR_ONE:
-            v = 1.0
-        elif self.var == VAR_X:
-            v = float(x[self.index])
-        elif self.var == VAR_XADD:
-            v = float(x_add[self.index])
-        elif self.var == VAR_TSTEP:
-            v = float(nt)
-        else:
-            raise ValueError(f"bad var {self.var}")
-        t = self.a * v + self.b
-        if self.func == FN_ONE:
-            f = 1.0
-        elif self.func == FN_LINEAR:
-            f = t
-        elif self.func == FN_COS:
-            f = np.cos(t)
-        elif self.func == FN_SIN:
-            f = np.sin(t)
-        elif self.func == FN_CIS:
-            f = complex(np.cos(t), np.sin(t))
-        else:
-            raise ValueError(f"bad func {self.func}")
+        f = _value(self.var, self.index, self.func, self.a, self.b, nt, x, x_add)
         s = complex(self.scale)
         if isinstance(f, complex) or s.imag != 0.0:
-            return s * f
-        return s.real * f  # real coefficient times complex operator, like the closures
+            c = s * f
+        else:
+            c = s.real * f  # real coefficient times complex operator, like the closures
+        for fac in self.factors:
+            c = c * fac.value(nt, x, x_add)
+        return c
+
+    def reads(self, var) -> bool:
+        """The term or one of its factors reads the variable kind `var`."""
+        return self.var == var or any(f.var == var for f in self.factors)
 
 
 def _accumulate(terms: Sequence[Term], nt, x, x_add, ndim):
@@ -89,7 +136,7 @@ class OperatorBasisHamiltonian:
         return _accumulate(self.terms, nt, x, x_add, self.ndim)
 
     def depends_on_xadd(self) -> bool:
-        return any(t.var == VAR_XADD for t in self.terms)
+        return any(t.reads(VAR_XADD) for t in self.terms)
 
 
 class OperatorBasisError:
@@ -117,6 +164,8 @@ class OperatorBasisTarget:
         for t in self.terms:
             if t.var in (VAR_X, VAR_TSTEP):
                 raise ValueError("target terms may only depend on x_add")
+            if t.factors:
+                raise ValueError("target terms take no factors")
 
     def __call__(self, x_add):
         return _accumulate(self.terms, 1, (), x_add, self.ndim)
@@ -205,22 +254,33 @@ class DescriptorBuffers:
                 ops.append(np.asarray(m, np.complex128))
             return index[key]
 
-        def cterms(terms):
-            arr = (CTerm * max(1, len(terms)))()
-            for i, t in enumerate(terms):
+        def rows(terms):  # one grape_term per Term, each followed by one op = -1 grape_term per Factor
+            out = []
+            for t in terms:
                 s = complex(t.scale)
-                arr[i] = CTerm(op_id(t.op), t.var, t.index, t.func, t.a, t.b, s.real, s.imag)
-            return arr
+                out.append(CTerm(op_id(t.op), t.var, t.index, t.func, t.a, t.b, s.real, s.imag))
+                for f in t.factors:
+                    out.append(CTerm(OP_FACTOR, f.var, f.index, f.func, f.a, f.b, float(f.scale), 0.0))
+            return out
 
-        self.h0 = cterms(up.H0.terms)
-        err_terms: List[Term] = []
-        offs = [0]
+        def cterms(terms):
+            out = rows(terms)
+            arr = (CTerm * max(1, len(out)))()
+            for i, r in enumerate(out):
+                arr[i] = r
+            return arr, len(out)
+
+        self.h0, n_h0 = cterms(up.H0.terms)
+        err_rows = []
+        offs = [0]  # offsets count the factor rows
         for es in up.error_sources:
-            err_terms.extend(es.Herror.terms)
-            offs.append(len(err_terms))
-        self.err = cterms(err_terms)
+            err_rows.extend(rows(es.Herror.terms))
+            offs.append(len(err_rows))
+        self.err = (CTerm * max(1, len(err_rows)))()
+        for i, r in enumerate(err_rows):
+            self.err[i] = r
         self.offs = (ctypes.c_int32 * len(offs))(*offs)
-        self.target = cterms(fp.target_unitary.terms)
+        self.target, _ = cterms(fp.target_unitary.terms)
         d = up.ndim
         stack = np.stack([np.asfortranarray(o) for o in ops])  # (n_ops, d, d)
         inter = np.empty((len(ops), d * d * 2), np.float64)
@@ -235,7 +295,7 @@ class DescriptorBuffers:
             ndim=d, ntimes=up.ntimes, nparam=nparam, nadd=up.nb_additional_param,
             nerr=len(up.error_sources), n_ops=len(ops), t0=float(up.t0), eps=float(up.eps),
             eps2=float(up.eps2), projector_diag=self.pdiag.ctypes.data_as(dp),
-            ops=self.ops.ctypes.data_as(dp), n_h0_terms=len(up.H0.terms), h0_terms=self.h0,
+            ops=self.ops.ctypes.data_as(dp), n_h0_terms=n_h0, h0_terms=self.h0,
             err_term_offsets=self.offs, err_terms=self.err,
             n_target_terms=len(fp.target_unitary.terms), target_terms=self.target,
             max_batch=int(max_batch), reserved=_reserved(0, options, scan_waves),

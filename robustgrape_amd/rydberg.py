@@ -14,7 +14,7 @@ import math
 import numpy as np
 
 from .operators import (FN_CIS, FN_COS, FN_ONE, FN_SIN, VAR_ONE, VAR_X, VAR_XADD,
-                        OperatorBasisError, OperatorBasisHamiltonian, OperatorBasisTarget, Term)
+                        Factor, OperatorBasisError, OperatorBasisHamiltonian, OperatorBasisTarget, Term)
 
 _S2 = math.sqrt(2.0)
 
@@ -126,43 +126,49 @@ def _phase_pair(ndim, couplings, scale_of):
     return Hc, Hs
 
 
-def _drive_terms(Hc, Hs, param=0):
-    return [Term(op=Hc, var=VAR_X, index=param, func=FN_COS),
-            Term(op=Hs, var=VAR_X, index=param, func=FN_SIN)]
+def _drive_terms(Hc, Hs, param=0, amplitude_param=None):
+    """cos(x[param]) Hc + sin(x[param]) Hs; with amplitude_param the drive is scaled by the control
+    x[amplitude_param] (a shaped pulse: a Factor on both terms)."""
+    factors = () if amplitude_param is None else (Factor(VAR_X, amplitude_param),)
+    return [Term(op=Hc, var=VAR_X, index=param, func=FN_COS, factors=factors),
+            Term(op=Hs, var=VAR_X, index=param, func=FN_SIN, factors=factors)]
 
 
-def rydberg_symmetric_blockaded_operator_basis(eps=0.0, delta=0.0, param=0):
-    """H0(nt, x, x_add) = rydberg_hamiltonian_symmetric_blockaded(x[param], eps, delta)."""
+def rydberg_symmetric_blockaded_operator_basis(eps=0.0, delta=0.0, param=0, amplitude_param=None):
+    """H0(nt, x, x_add) = rydberg_hamiltonian_symmetric_blockaded(x[param], eps, delta); with
+    amplitude_param the couplings are scaled by the control x[amplitude_param] (amplitude x phase)."""
     Hc, Hs = _phase_pair(5, _SYM_COUPLINGS, lambda _: 1.0 + eps)
-    terms = _drive_terms(Hc, Hs, param)
+    terms = _drive_terms(Hc, Hs, param, amplitude_param)
     if delta != 0.0:
         terms.append(Term(op=np.diag([0, 0, 0, delta, delta]).astype(np.complex128)))
     return OperatorBasisHamiltonian(terms)
 
 
-def rydberg_full_blockaded_operator_basis(eps=0.0, delta=0.0, param=0):
-    """H0 = rydberg_hamiltonian_full_blockaded(x[param], eps, delta)."""
+def rydberg_full_blockaded_operator_basis(eps=0.0, delta=0.0, param=0, amplitude_param=None):
+    """H0 = rydberg_hamiltonian_full_blockaded(x[param], eps, delta) (amplitude_param: as above)."""
     Hc, Hs = _phase_pair(7, _FULLBLK_COUPLINGS, lambda _: 1.0 + eps)
-    terms = _drive_terms(Hc, Hs, param)
+    terms = _drive_terms(Hc, Hs, param, amplitude_param)
     if delta != 0.0:
         terms.append(Term(op=np.diag([0, 0, 0, 0, delta, delta, delta]).astype(np.complex128)))
     return OperatorBasisHamiltonian(terms)
 
 
-def rydberg_full_operator_basis(O1=1.0, O2=1.0, d1=0.0, d2=0.0, B=10.0, param=0):
-    """H0 = rydberg_hamiltonian_full(x[param], O1, O2, d1, d2, B)."""
+def rydberg_full_operator_basis(O1=1.0, O2=1.0, d1=0.0, d2=0.0, B=10.0, param=0, amplitude_param=None):
+    """H0 = rydberg_hamiltonian_full(x[param], O1, O2, d1, d2, B) (amplitude_param: both Rabi
+    frequencies scaled by the control x[amplitude_param])."""
     Hc, Hs = _phase_pair(9, _FULL_COUPLINGS, lambda w: O1 if w == 1 else O2)
-    terms = _drive_terms(Hc, Hs, param)
+    terms = _drive_terms(Hc, Hs, param, amplitude_param)
     Hd = np.diag([0, 0, 0, 0, d1, d2, d1, d2, d1 + d2 + B]).astype(np.complex128)
     if np.any(Hd != 0):
         terms.append(Term(op=Hd))
     return OperatorBasisHamiltonian(terms)
 
 
-def symmetric_amplitude_error(param=0):
-    """Herror = H(phi, err, 0) - H(phi, 0, 0) for the d=5 model (runtests.jl:59)."""
+def symmetric_amplitude_error(param=0, amplitude_param=None):
+    """Herror = H(phi, err, 0) - H(phi, 0, 0) for the d=5 model (runtests.jl:59); with amplitude_param
+    the relative amplitude error of the shaped drive, err * x[amplitude_param] * (couplings)."""
     Hc, Hs = _phase_pair(5, _SYM_COUPLINGS, lambda _: 1.0)
-    return OperatorBasisError(_drive_terms(Hc, Hs, param))
+    return OperatorBasisError(_drive_terms(Hc, Hs, param, amplitude_param))
 
 
 def symmetric_frequency_error():
@@ -170,19 +176,20 @@ def symmetric_frequency_error():
     return OperatorBasisError([Term(op=np.diag([0, 0, 0, 1, 1]).astype(np.complex128))])
 
 
-def full_blockaded_amplitude_error(param=0):
+def full_blockaded_amplitude_error(param=0, amplitude_param=None):
     Hc, Hs = _phase_pair(7, _FULLBLK_COUPLINGS, lambda _: 1.0)
-    return OperatorBasisError(_drive_terms(Hc, Hs, param))
+    return OperatorBasisError(_drive_terms(Hc, Hs, param, amplitude_param))
 
 
 def full_blockaded_frequency_error():
     return OperatorBasisError([Term(op=np.diag([0, 0, 0, 0, 1, 1, 1]).astype(np.complex128))])
 
 
-def full_rabi_error(which, param=0):
-    """d=9: Omega_which -> Omega_which + err."""
+def full_rabi_error(which, param=0, amplitude_param=None):
+    """d=9: Omega_which -> Omega_which + err; with amplitude_param the error scales
+    with the drive's amplitude control."""
     Hc, Hs = _phase_pair(9, _FULL_COUPLINGS, lambda w: 1.0 if w == which else 0.0)
-    return OperatorBasisError(_drive_terms(Hc, Hs, param))
+    return OperatorBasisError(_drive_terms(Hc, Hs, param, amplitude_param))
 
 
 def full_detuning_error(which):

@@ -1,17 +1,20 @@
 """Register / scratch / occupancy of every kernel of one translation unit (hipcc's
 -Rpass-analysis=kernel-resource-usage remarks), one line per kernel.
-    python scripts/kernel_resources.py robustgrape_amd/csrc/grape_walk_inst.hip [name-filter]"""
+    python scripts/kernel_resources.py robustgrape_amd/csrc/grape_walk_inst.hip [name-filter] [-DNAME=VALUE ...]
+Arguments that start with a dash go to the compiler (the per-dimension units need -DGRAPE_INST_DIM=<d>)."""
 import os
 import re
 import subprocess
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-src = sys.argv[1]
-filt = sys.argv[2] if len(sys.argv) > 2 else ""
+flags = [a for a in sys.argv[1:] if a.startswith("-")]
+args = [a for a in sys.argv[1:] if not a.startswith("-")]
+src = args[0]
+filt = args[1] if len(args) > 1 else ""
 cmd = ["/opt/rocm/bin/hipcc", "-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "-ffp-contract=off",
        "-I" + os.path.join(ROOT, "include"), "-I" + os.path.join(ROOT, "robustgrape_amd", "csrc"),
-       "-Rpass-analysis=kernel-resource-usage", "-c", src, "-o", "/dev/null"]
+       "-Rpass-analysis=kernel-resource-usage"] + flags + ["-c", src, "-o", "/dev/null"]
 if "walk" in src:
     cmd[1:1] = ["-mllvm", "-disable-machine-licm"]
 out = subprocess.run(cmd, capture_output=True, text=True).stderr
