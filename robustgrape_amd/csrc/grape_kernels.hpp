@@ -91,7 +91,7 @@ struct DevProblem {
     const cd *PA;        // P0 P  (row-major), P = P0 with nonzeros set to 1
     const cd *PB;        // P     (row-major)
     const cd *P0g;       // P0    (row-major; expectation values)
-    // Sectors (grape_engine.hip find_sectors): when every operator H0 uses is block-diagonal in
+    // Sectors (grape_plan_setup.hpp find_sectors): when every operator H0 uses is block-diagonal in
     // a common permutation, one evaluation is run as nsec independent D x D sector problems
     // (sub-evaluation b' = b * nsec + w reads x of b and the operators of sector w at
     // ops / opsT + w * sec_ops); k_scan stops after the chunk carries, the sector head

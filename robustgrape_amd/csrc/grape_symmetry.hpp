@@ -1,7 +1,7 @@
 // grape_symmetry.hpp -- symmetry-adapted sectors: the finest block decomposition of the operator
 // algebra (host code, plan creation only).
 //
-// The sector engine (grape_engine.hip find_sectors) splits the levels into the connected components
+// The sector engine (grape_plan_setup.hpp find_sectors) splits the levels into the connected components
 // of the operators' union sparsity pattern: a PERMUTATION of the basis.  A symmetry can split a
 // component further in a rotated basis.  In rydberg_hamiltonian_full with equal Rabi frequencies and
 // detunings (the BASELINE C2 configuration, RydbergTools.jl:118-130) the atom-swap symmetry splits

@@ -1,0 +1,273 @@
+"""Block-structure problems for the sector path (grape_plan_setup.hpp find_sectors, grape_engine.hip
+symmetry_setup / setup_sector_head / decide_class) beyond the three Rydberg Hamiltonians: seeded random
+Hermitian blocks over the public Term / OperatorBasis* types, plain numpy.
+
+A problem is a tuple of component sizes (`comps`) plus `nfixed` levels no operator touches.  In canonical
+order the components' levels are consecutive and the fixed levels come last; a seeded permutation then
+scatters the labels (tests/problems.py relabel's convention: Pi e_i = e_perm[i]) so that no component is
+contiguous and the components interleave.
+
+    H0(k, x, x_add) = Hd + x[0] Hc0  [+ cos(a x[1] + b) Hc1 + sin(a x[1] + b) Hs1]  [+ x_add[1] Nd]
+    Herror_0 = x[0] Hc0 [+ 0.3 cos(x_add[1]) Nd],  Herror_1 = diagonal,  Herror_e = random blocks (e >= 2)
+    (Hc0 a unit random operator, every other one REST times one)
+    U0(theta) = [Q] diag(e^{i alpha_j}) (Pi0 + cis(theta) Pi1),  theta = x_add[0]
+
+with dt = 1 and every H0 / Herror operator scaled by one factor so that max_k |dt H0|_1 over the problem's
+own controls (block_x) is `step_norm`.
+
+CASES is the layout table the tests pin (tests/test_sector_shapes_cpu.py through tests/c/sectors_check.cpp
+on the host, tests/test_gpu_sector_shapes.py on the device): name -> (block_problem arguments, layout with
+GRAPE_OPT_NO_SYMMETRY in GrapePlan.sectors() notation)."""
+from __future__ import annotations
+
+import math
+
+import numpy as np
+
+from robustgrape_amd.operators import (FN_CIS, FN_COS, FN_LINEAR, FN_SIN, VAR_X, VAR_XADD, OperatorBasisError,
+                                       OperatorBasisHamiltonian, OperatorBasisTarget, Term)
+from robustgrape_amd.types import ErrorSource, FidelityRobustGRAPEProblem, UnitaryRobustGRAPEProblem
+from tests import problems as P
+
+PHASE_A, PHASE_B = -1.5, 0.4    # the second control enters as cos / sin(a x[1] + b)
+X_ROWS = 5                      # controls per problem: the rows the operators' scale is fixed on
+# The linear control lives on [-X_MAX, X_MAX) and every other operator is REST times a unit random one, so that
+# x[0] Hc0 and the rest of H0 have the same size while Hc0 itself is large: dF/dx[0] is then of order 0.1 to 1
+# at |dt H0|_1 = 0.2.  Every double implementation's forward difference carries u / eps ~ 1e-8 of absolute
+# noise; the short-step tier (1e-7 max|F_dx| + 1e-9) only discriminates above it for gradients of that size.
+X_MAX = REST = 0.005
+
+
+def block_x(ntimes, seed, nparam=1, na=1, rows=X_ROWS):
+    """The problem's controls, (rows, n_x): x[0] ~ U[-X_MAX, X_MAX), x[1] ~ U[-1, 1), theta = x_add[0] ~ 2 pi U,
+    x_add[1] ~ U[-0.5, 0.5)."""
+    rng = np.random.default_rng([int(seed), ntimes, nparam, 1234])
+    X = np.empty((rows, ntimes * nparam + na))
+    X[:, :ntimes * nparam] = rng.uniform(-1.0, 1.0, size=(rows, ntimes * nparam))
+    X[:, 0:ntimes * nparam:nparam] *= X_MAX
+    X[:, ntimes * nparam] = 2 * math.pi * rng.uniform(size=rows)
+    if na == 2:
+        X[:, ntimes * nparam + 1] = rng.uniform(-0.5, 0.5, size=rows)
+    return X
+
+
+def _ranges(comps):
+    out, o = [], 0
+    for n in comps:
+        out.append(np.arange(o, o + n))
+        o += n
+    return out
+
+
+def scatter_permutation(comps, nfixed, seed):
+    """perm[i]: the label of canonical level i.  No component of two or more levels keeps consecutive labels."""
+    d = sum(comps) + nfixed
+    rng = np.random.default_rng([int(seed), 77])
+    for _ in range(10000):
+        perm = rng.permutation(d)
+        if all(len(r) < 2 or len(r) == d or np.ptp(perm[r]) > len(r) - 1 for r in _ranges(comps)):
+            return perm
+    raise ValueError("no scattering permutation found")
+
+
+def block_layout(comps, nfixed, seed, scatter=True):
+    """(perm, the labels of every component in ascending order, the fixed labels in ascending order)."""
+    d = sum(comps) + nfixed
+    perm = scatter_permutation(comps, nfixed, seed) if scatter else np.arange(d)
+    return perm, [np.sort(perm[r]) for r in _ranges(comps)], np.sort(perm[sum(comps):])
+
+
+def default_weights(comps, nfixed, seed):
+    """Projector weights in canonical order: one weighted level per component of two or more levels, never the one
+    with the component's lowest label (the first slot of its sector), the values 2, 1, 0.5, 1.5 in turn; 1.5 / 0.75
+    on the lone levels, 1 / 0.7 on the fixed ones; zero elsewhere."""
+    perm = scatter_permutation(comps, nfixed, seed)
+    w = np.zeros(sum(comps) + nfixed)
+    vals, lone, nl = (2.0, 1.0, 0.5, 1.5), (1.5, 0.75), 0
+    for ci, r in enumerate(_ranges(comps)):
+        if len(r) == 1:
+            w[r[0]] = lone[nl % 2]
+            nl += 1
+        else:
+            order = r[np.argsort(perm[r])]  # the component's canonical levels by ascending label
+            w[order[1 + ci % (len(r) - 1)]] = vals[ci % 4]
+    for f in range(nfixed):
+        w[sum(comps) + f] = 1.0 if f == 0 else 0.7
+    return w
+
+
+def _herm(rng, n):
+    h = rng.normal(size=(n, n)) + 1j * rng.normal(size=(n, n))
+    return (h + h.conj().T) / 2
+
+
+def block_problem(comps, nfixed, ntimes, *, seed, nparam=1, nerr=0, xadd_h0=False, target="diag", weights=None,
+                  hidden=False, step_norm=0.2, device=True, identical=(), err_couples=None, scatter=True):
+    """The FidelityRobustGRAPEProblem of the module docstring.
+
+    weights: the projector's diagonal in canonical order (default_weights when None).
+    hidden: every H0 and error operator conjugated by one random complex unitary W; target and projector stay
+    as they are (no permutation sectors then: only the symmetry basis finds the blocks).
+    identical: pairs (i, j) of equal-sized components; j carries i's block in every operator (multiplicity two).
+    err_couples: (i, j) -- error source 0 also couples components i and j (the error operators enter the pattern).
+    scatter=False: the canonical level order (the same physics as scatter=True).
+    device=False: the same matrices from plain closures calling the operator-basis objects."""
+    comps = tuple(int(n) for n in comps)
+    nlive = sum(comps)
+    d = nlive + nfixed
+    assert nparam in (1, 2) and target in ("diag", "dense") and all(n >= 1 for n in comps)
+    rng = np.random.default_rng([int(seed), 1])
+    ranges = _ranges(comps)
+    twin = {j: i for i, j in identical}
+
+    def blocks(lone_diag=False):  # a random Hermitian operator with exactly these components, fully coupled
+        H = np.zeros((d, d), np.complex128)
+        for ci, r in enumerate(ranges):
+            if ci in twin:
+                H[np.ix_(r, r)] = H[np.ix_(ranges[twin[ci]], ranges[twin[ci]])]
+            elif len(r) > 1:
+                H[np.ix_(r, r)] = _herm(rng, len(r))
+            elif lone_diag:
+                H[r[0], r[0]] = rng.uniform(0.5, 1.5) * rng.choice([-1.0, 1.0])
+        return H
+
+    def diagonal():  # real, on every level of a component
+        H = np.zeros((d, d), np.complex128)
+        for ci, r in enumerate(ranges):
+            v = H[ranges[twin[ci]], ranges[twin[ci]]] if ci in twin else rng.uniform(-1.0, 1.0, size=len(r))
+            H[r, r] = v
+        return H
+
+    Hd, Hc0 = REST * blocks(lone_diag=True), blocks()
+    Hc1, Hs1 = (REST * blocks(), REST * blocks()) if nparam == 2 else (None, None)
+    Nd = 2 * REST * diagonal() if xadd_h0 else None
+    err_ops = []
+    for e in range(nerr):
+        op = Hc0.copy() if e == 0 else REST * diagonal() if e == 1 else REST * blocks()
+        if e == 0 and err_couples is not None:
+            ri, rj = ranges[err_couples[0]], ranges[err_couples[1]]
+            c = rng.normal(size=(len(ri), len(rj))) + 1j * rng.normal(size=(len(ri), len(rj)))
+            op[np.ix_(ri, rj)] = c
+            op[np.ix_(rj, ri)] = c.conj().T
+        err_ops.append(op)
+    # target and projector
+    alpha = rng.uniform(0, 2 * math.pi, size=d)
+    in1 = np.zeros(d, bool)
+    in1[rng.permutation(d)[:max(1, d // 2)]] = True
+    D = np.diag(np.exp(1j * alpha))
+    T0, T1 = D @ np.diag((~in1).astype(float)), D @ np.diag(in1.astype(float))
+    if target == "dense":
+        Q, _ = np.linalg.qr(rng.normal(size=(d, d)) + 1j * rng.normal(size=(d, d)))
+        T0, T1 = Q @ T0, Q @ T1
+    w = default_weights(comps, nfixed, seed) if weights is None else np.asarray(weights, np.float64)
+    assert w.shape == (d,) and np.all(w >= 0)
+    Wm = np.diag(w)
+    # level order
+    perm = scatter_permutation(comps, nfixed, seed) if (scatter and not hidden) else np.arange(d)
+
+    def moved(M):
+        out = np.zeros((d, d), np.complex128)
+        out[np.ix_(perm, perm)] = M
+        return out
+    hams = [Hd, Hc0] + ([Hc1, Hs1] if nparam == 2 else []) + ([Nd] if xadd_h0 else [])
+    if hidden:
+        Wu, _ = np.linalg.qr(rng.normal(size=(d, d)) + 1j * rng.normal(size=(d, d)))
+        conj = lambda M: Wu @ M @ Wu.conj().T  # noqa: E731
+        hams, err_ops = [conj(M) for M in hams], [conj(M) for M in err_ops]
+    hams, err_ops = [moved(M) for M in hams], [moved(M) for M in err_ops]
+    T0, T1, Wm = moved(T0), moved(T1), moved(Wm).real
+    na = 2 if xadd_h0 else 1
+
+    def build(scale):
+        hs = [scale * M for M in hams]
+        terms = [Term(hs[0]), Term(hs[1], var=VAR_X, index=0, func=FN_LINEAR)]
+        k = 2
+        if nparam == 2:
+            terms += [Term(hs[2], var=VAR_X, index=1, func=FN_COS, a=PHASE_A, b=PHASE_B),
+                      Term(hs[3], var=VAR_X, index=1, func=FN_SIN, a=PHASE_A, b=PHASE_B)]
+            k = 4
+        if xadd_h0:
+            terms.append(Term(hs[k], var=VAR_XADD, index=1, func=FN_LINEAR))
+        errs = []
+        for e, M in enumerate(err_ops):
+            if e == 0 and err_couples is None:
+                et = [Term(hs[1], var=VAR_X, index=0, func=FN_LINEAR)]  # the control operator itself
+            elif e == 0:
+                et = [Term(scale * M, var=VAR_X, index=0, func=FN_LINEAR)]
+            else:
+                et = [Term(scale * M)]
+            if e == 0 and xadd_h0:
+                et.append(Term(hs[k], var=VAR_XADD, index=1, func=FN_COS, scale=0.3))
+            errs.append(ErrorSource(OperatorBasisError(et)))
+        up = UnitaryRobustGRAPEProblem(t0=float(ntimes), ntimes=ntimes, ndim=d, H0=OperatorBasisHamiltonian(terms),
+                                       nb_additional_param=na, error_sources=errs)
+        tgt = OperatorBasisTarget([Term(T0), Term(T1, var=VAR_XADD, index=0, func=FN_CIS)])
+        return FidelityRobustGRAPEProblem(up, Wm, tgt)
+
+    X = block_x(ntimes, seed, nparam, na)
+    fp = build(step_norm / P.max_step_norm(build(1.0), X, nparam))
+    if device:
+        return fp
+    up = fp.unitary_problem
+    Hdev, tdev = up.H0, fp.target_unitary
+    errs = [ErrorSource(lambda t, x, xa, e, h=es.Herror: h(t, x, xa, e)) for es in up.error_sources]
+    return fp.replace(unitary_problem=up.replace(H0=lambda t, x, xa: Hdev(t, x, xa), error_sources=errs),
+                      target_unitary=lambda xa: tdev(xa))
+
+
+def dense_projector(d, seed, rank=3):
+    """A dense real rank-3 orthogonal projector (tests/test_gpu_projector.py dense_projector)."""
+    Qm, _ = np.linalg.qr(np.random.default_rng(seed).standard_normal((d, rank)))
+    return Qm @ Qm.T
+
+
+def _idle_weights(comps, nfixed, seed):
+    w = default_weights(comps, nfixed, seed)
+    for r in _ranges(comps):
+        if len(r) == 1:
+            w[r[0]] = 0.0
+    return w
+
+
+# name -> (comps, nfixed, further block_problem arguments, layout with GRAPE_OPT_NO_SYMMETRY)
+CASES = {
+    "q3333": ((3, 3, 3, 3), 0, dict(seed=11), ((3, 4),)),
+    "c3221": ((3, 2, 2, 1), 0, dict(seed=212), ((3, 1), (2, 3))),
+    "c3221-idle": ((3, 2, 2, 1), 0, dict(seed=212, weights=_idle_weights((3, 2, 2, 1), 0, 212)), ((3, 1), (2, 2))),
+    "c431": ((4, 3, 1), 0, dict(seed=13), ((4, 2),)),
+    "c44ff": ((4, 4), 2, dict(seed=114), ((4, 2),)),
+    "c222222": ((2,) * 6, 0, dict(seed=15), ((2, 6),)),
+    "diag6": ((1,) * 6, 0, dict(seed=16), ((2, 3),)),
+    "c55": ((5, 5), 0, dict(seed=17), ((5, 2),)),
+    "c66": ((6, 6), 0, dict(seed=18), ((6, 2),)),
+    "c4321f": ((4, 3, 2, 1), 1, dict(seed=19), ((4, 1), (3, 2))),
+    "c532f": ((5, 3, 2), 1, dict(seed=220), ((5, 1), (3, 2))),
+    "merge": ((2, 2, 2, 2), 0, dict(seed=21, nerr=1, err_couples=(1, 3)), ((4, 1), (2, 2))),
+}
+MERGE_WITHOUT = ((2, 4),)   # the merge case without its error source
+
+# hidden-block cases: name -> (comps, further arguments, layout with the symmetry basis on)
+HIDDEN = {
+    "h32": ((3, 2), dict(seed=431), ((3, 1), (2, 1))),
+    "h43": ((4, 3), dict(seed=432), ((4, 1), (3, 1))),
+    "h444": ((4, 4, 4), dict(seed=333), ((4, 3),)),
+    "h3+22": ((3, 2, 2), dict(seed=34, identical=((1, 2),)), ((3, 1), (2, 2))),
+}
+
+
+def case_problem(name, ntimes, **over):
+    """The table case `name` (CASES or HIDDEN) at `ntimes` steps; `over` overrides block_problem arguments."""
+    if name in CASES:
+        comps, nfixed, kw, _ = CASES[name]
+        kw = dict(kw)
+    else:
+        comps, kw, _ = HIDDEN[name]
+        nfixed, kw = 0, dict(kw, hidden=True)
+    kw.update(over)
+    return block_problem(comps, nfixed, ntimes, **kw)
+
+
+def case_x(name, ntimes, nparam=1, na=1):
+    """The controls the case's operators were scaled on (block_x with the case's seed)."""
+    seed = (CASES[name][2] if name in CASES else HIDDEN[name][1])["seed"]
+    return block_x(ntimes, seed, nparam, na)
