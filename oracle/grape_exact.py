@@ -23,6 +23,8 @@ the reference means to return, against which the noise of the oracle, the C++ po
 paths can each be read off (scripts/probes/fd_exact_probe.py, tests/test_gpu_gauge.py).
 
 Scope: no error sources (F, F_dx, F_dx_add), H0 free of x_add (the target part of F_dx_add only).
+Every step's H0 (and H0 + Herror in the evaluators with error sources) must be Hermitian to rounding: the
+chain's inverse is taken as C_k^dagger, so anything else raises ValueError (_require_hermitian).
 """
 from __future__ import annotations
 
@@ -113,6 +115,15 @@ def _check_scope(up):
             raise ValueError("grape_exact covers Herror independent of x_add (it takes U_derr_dx_add = 0)")
 
 
+def _require_hermitian(H, what, k):
+    """The evaluators take C_k^-1 = C_k^dagger, which holds for unitary propagators only: a generator that is not
+    Hermitian to rounding (e.g. a -i Gamma / 2 decay term) is refused instead of evaluated wrongly."""
+    dev = float(np.max(np.abs(H - H.conj().T)))
+    if not dev <= 1e-12 * max(float(np.max(np.abs(H))), 1e-300):
+        raise ValueError(f"grape_exact covers Hermitian generators (it takes C_k^-1 = C_k^dagger): {what} at step "
+                         f"{k} is {dev:.1e} from Hermitian")
+
+
 def fidelity_and_gradient(fp, x, nparam=1):
     """(F, F_dx_tot) of calculate_fidelity_and_derivatives(fp, x), evaluated in longdouble."""
     up = fp.unitary_problem
@@ -127,7 +138,9 @@ def fidelity_and_gradient(fp, x, nparam=1):
     xa = x[len(x) - na:].copy()
     Es, dEs = [], []
     for k in range(nt):
-        E = exp_ld(LD(-1j * dt) * _h0_ld(up.H0, k + 1, xm[k], xa))
+        H0k = _h0_ld(up.H0, k + 1, xm[k], xa)
+        _require_hermitian(H0k, "H0", k + 1)
+        E = exp_ld(LD(-1j * dt) * H0k)
         Es.append(E)
         row = []
         for p in range(nparam):
@@ -200,6 +213,7 @@ def fidelity_and_derivatives(fp, x, nparam=1):
     for k in range(nt):
         xk = xm[k].copy()
         H0k = _h0_ld(up.H0, k + 1, xk, xa)
+        _require_hermitian(H0k, "H0", k + 1)
         E = exp_ld(cdt * H0k)
         Cold, C = C, E @ C
         Ci = ct(C)  # the unitary chain's inverse (exact here to 1e-19)
@@ -211,7 +225,9 @@ def fidelity_and_derivatives(fp, x, nparam=1):
             xp[p] = xk[p] + eps2
             Edx2.append(exp_ld(cdt * _h0_ld(up.H0, k + 1, xp, xa)))
         for e, src in enumerate(up.error_sources):
-            E1 = exp_ld(cdt * (_herr_ld(src, k + 1, xk, xa, eps) + H0k))
+            H1 = _herr_ld(src, k + 1, xk, xa, eps) + H0k
+            _require_hermitian(H1, f"H0 + Herror_{e}", k + 1)
+            E1 = exp_ld(cdt * H1)
             Verr[e, k] = Ci @ ((E1 - E) / LD(eps)) @ Cold
             E2 = exp_ld(cdt * (_herr_ld(src, k + 1, xk, xa, eps2) + H0k))
             for p in range(nparam):
@@ -298,11 +314,14 @@ def sensitivities_and_xadd(fp, x, nparam=1):
     for k in range(nt):
         xk = xm[k].copy()
         H0k = _h0_ld(up.H0, k + 1, xk, xa)
+        _require_hermitian(H0k, "H0", k + 1)
         E = exp_ld(cdt * H0k)
         Cold, C = C, E @ C
         Ci = ct(C)
         for e, src in enumerate(up.error_sources):
-            E1 = exp_ld(cdt * (_herr_ld(src, k + 1, xk, xa, eps) + H0k))
+            H1 = _herr_ld(src, k + 1, xk, xa, eps) + H0k
+            _require_hermitian(H1, f"H0 + Herror_{e}", k + 1)
+            E1 = exp_ld(cdt * H1)
             Ssum[e] = Ssum[e] + Ci @ ((E1 - E) / LD(eps)) @ Cold
     U = C
     P0 = np.asarray(fp.projector, dtype=np.complex128)

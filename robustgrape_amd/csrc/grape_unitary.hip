@@ -135,9 +135,12 @@ __global__ __launch_bounds__(BLOCK) void k_u_inverse(UProblem P, const cd *C, cd
                     M[pr * D + j] = a;
                 }
             tsync();
+            // 1 / pivot with the pivot scaled by its larger part first: |pivot|^2 itself underflows for a pivot
+            // below 1.5e-154 (a strongly decayed level), whose reciprocal is still a finite double
             const cd pv = sA[c * D + c];
-            const double den = pv.re * pv.re + pv.im * pv.im;
-            const cd rp{pv.re / den, -pv.im / den};
+            const double sc = fmax(fabs(pv.re), fabs(pv.im));  // > 0: the pivot search found a nonzero entry
+            const double qr = pv.re / sc, qi = pv.im / sc, den = qr * qr + qi * qi;
+            const cd rp{qr / den / sc, -qi / den / sc};
             tsync();
             for (int t = t0; t < 2 * D; t += blockDim.x) {  // pivot row * (1 / pivot)
                 cd *M = t < D ? sA : sI;
