@@ -574,7 +574,10 @@ int grape_symmetry_basis(const grape_desc *desc, double *V, int *block);
  * Above GRAPE_MAX_DENSE_DIM the tiled engine's solve-free exponential runs (Taylor of A / 2^s with
  * |A / 2^s|_1 <= 0.95, then s squarings; grape_tiled.hpp): the result agrees with exp! to rounding.
  * stats (optional, 5 ints) receives how many matrices used Pade m=3,5,7,9,13 (above
- * GRAPE_MAX_SMALL_DIM: Julia's degree choice for |A|_1, the same histogram on every engine).
+ * GRAPE_MAX_SMALL_DIM: Julia's degree choice for |A|_1, the same histogram on every engine for
+ * a matrix that is not diagonal).  A diagonal A counts in the first slot up to GRAPE_MAX_SMALL_DIM,
+ * whatever its norm: there exp!'s isdiag shortcut returns before any degree is chosen; the dense and
+ * tiled engines have no shortcut and count it by its 1-norm like any other matrix.
  * For a general A above GRAPE_MAX_SMALL_DIM use grape_expm_batch_general.
  */
 int grape_expm_batch(int device, int ndim, int n, const double *A, double *E, int *stats);

@@ -34,6 +34,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "grape_pade_degree.hpp"
+
 namespace grape {
 
 struct cd {
@@ -286,19 +288,7 @@ __constant__ const double kPade13[14] = {64764752532480000.0, 32382376266240000.
                                          670442572800.0, 33522128640.0, 1323241920.0,
                                          40840800.0, 960960.0, 16380.0, 182.0, 1.0};
 
-// Degree choice of exp! for a 1-norm: returns m, writes s (squarings).
-__device__ __forceinline__ int pade_degree(double nA, int &s) {
-    s = 0;
-    if (nA <= 2.1) {
-        if (nA > 0.95) return 9;
-        if (nA > 0.25) return 7;
-        if (nA > 0.015) return 5;
-        return 3;
-    }
-    const double l = log2(nA / 5.4);
-    if (l > 0.0) s = (int)ceil(l);
-    return 13;
-}
+// Degree choice of exp! for a 1-norm (m, s squarings): pade_degree, grape_pade_degree.hpp
 
 // ---------------------------------------------------------------------------
 // gesv(Y, X): solve Y Z = X in place (Z returned in x), LAPACK semantics

@@ -19,7 +19,8 @@ def _need_gpu():
         pytest.skip("no GPU")
 
 
-def random_problem(d, ntimes, nerr, device, seed=0):
+def random_problem(d, ntimes, nerr, device, seed=0, scale=1.0):
+    """scale multiplies dt, hence every step's |dt H|_1 (1.0: at most 0.125 (3 + |x_1|), no step beyond Pade 7)."""
     from robustgrape_amd.operators import (FN_CIS, FN_COS, FN_LINEAR, FN_SIN, VAR_X, VAR_XADD,
                                            OperatorBasisError, OperatorBasisHamiltonian,
                                            OperatorBasisTarget, Term)
@@ -43,7 +44,7 @@ def random_problem(d, ntimes, nerr, device, seed=0):
         H0 = lambda t, x, xa: Hdev(t, x, xa)  # noqa: E731
         tgt = lambda xa: tdev(xa)  # noqa: E731
         errs = [ErrorSource(lambda t, x, xa, e, es=es: es.Herror(t, x, xa, e)) for es in edev]
-    up = UnitaryRobustGRAPEProblem(t0=2.0 * ntimes / 16, ntimes=ntimes, ndim=d, H0=H0, nb_additional_param=1,
+    up = UnitaryRobustGRAPEProblem(t0=2.0 * ntimes / 16 * scale, ntimes=ntimes, ndim=d, H0=H0, nb_additional_param=1,
                                    error_sources=errs)
     half = max(1, d // 2)
     W = np.diag([1.0] * half + [0.0] * (d - half))
