@@ -18,6 +18,8 @@ CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libgrape.so")
 OBJ = os.path.join(HERE, "_obj")
 ENGINE = os.path.join(CSRC, "grape_engine.hip")
+# the other host units of the C ABI (grape_plan.hpp): descriptor logic, plan construction, call path, analysis
+HOST = [os.path.join(CSRC, f"grape_{n}.hip") for n in ("descriptor", "plan_build", "call", "analysis")]
 INST = os.path.join(CSRC, "grape_inst.hip")
 PROD = os.path.join(CSRC, "grape_prod_inst.hip")
 DENSE = os.path.join(CSRC, "grape_dense.hip")
@@ -28,7 +30,7 @@ WALK = os.path.join(CSRC, "grape_walk_inst.hip")
 EVAL1 = os.path.join(CSRC, "grape_eval1.hip")
 TILED = os.path.join(CSRC, "grape_tiled.hip")
 DIMS = list(range(2, 13))  # GRAPE_DIMS in grape_launch.hpp; GRAPE_MAX_SMALL_DIM = 12
-SOURCES = [ENGINE, INST, PROD, DENSE, UNITARY, LBFGS, PROJ, WALK, EVAL1, TILED]
+SOURCES = [ENGINE] + HOST + [INST, PROD, DENSE, UNITARY, LBFGS, PROJ, WALK, EVAL1, TILED]
 # every source and header of the library (an #include of a file that is not here would not reach source_id():
 # tests/test_capi_cpu.py checks the includes), the C ABI last
 DEPS = sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".hip", ".hpp"))) + \
@@ -100,6 +102,9 @@ def _units(defines):
     units += [(INST, [f"-DGRAPE_INST_DIM={d}"], os.path.join(sub, f"grape_inst_d{d}.o")) for d in DIMS]
     # the product-coefficient kernels (grape_prod.hpp), a unit of their own per dimension
     units += [(PROD, [f"-DGRAPE_INST_DIM={d}"], os.path.join(sub, f"grape_prod_d{d}.o")) for d in DIMS]
+    # the C ABI's other host units, plain flags.  Last: build_library() starts a unit when the oldest one in
+    # flight ends, so these few seconds each must not stand in the queue before the per-dimension units
+    units += [(src, [], os.path.join(sub, os.path.basename(src)[:-4] + ".o")) for src in HOST]
     return sub, units
 
 

@@ -243,7 +243,7 @@ hipError_t launch_pipeline(const DevProblem &P, const DevBatch &B, const grape::
 
 // Sectors (P.sectors, D = the sector size of one class, B.nb = evaluations x nsec).  Stage 0:
 // nominal sector propagators (every variant with error sources) -> sector scans (U_w,
-// carries).  Then (grape_engine.hip) the sector head over every class (F, the blocks of M,
+// carries).  Then (grape_call.hip) the sector head over every class (F, the blocks of M,
 // target part).  Stage 1: per-chunk images M'_c (k_sec_mc), then without error sources the
 // eps-variant sector exps contracted in place, with error sources the local-frame images (and
 // F_dx terms) and the sector error scans (Tot blocks, T_c, Ttot_c).  Then the sector error

@@ -1,4 +1,4 @@
-// grape_plan_setup.hpp -- host-side pieces of plan construction (grape_engine.hip): the propagator
+// grape_plan_setup.hpp -- host-side pieces of plan construction (grape_plan_build.hip): the propagator
 // variant list, the owner of a plan's device allocations, the operator / projector tile layouts, and the
 // sector layout rule (find_sectors).
 // Host code only: no kernel and no launch.

@@ -104,7 +104,7 @@ __device__ double btrprod(const cd *X, const cd *Y, int D, double *red) {
     return bsum(s, red);
 }
 
-// dense-engine register-file image (grape_engine.hip to_dense_image): element (row, col)
+// dense-engine register-file image (grape_plan_build.hip to_dense_image): element (row, col)
 __device__ __forceinline__ size_t img_off(int row, int col) {
     const int w = col >> 4, t = row >> 4, r = (row & 15) >> 2, l = ((row & 3) << 4) | (col & 15);
     return (size_t)((w * 4 + t) * 4 + r) * 64 + l;

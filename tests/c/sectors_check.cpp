@@ -2,7 +2,7 @@
 //   d n_ops n_h0 nerr options          (options: GRAPE_OPT_* of grape_desc.reserved[1])
 //   op ...                             (n_h0 operator indices: H0's terms)
 //   n op ...                           (one line per error source: its terms' operator indices)
-//   idle_0 ... idle_{d-1}              (0 / 1: grape_engine.hip idle_levels, stated by the caller)
+//   idle_0 ... idle_{d-1}              (0 / 1: grape_descriptor.hip idle_levels, stated by the caller)
 //   then per operator: nnz, and nnz lines "row col re im"
 // Output: first line "ncls nfixed"; per class a line "S nsec" and a line of nsec * S slot levels (sidx, -1:
 // padding); last the fixed levels.  Host code only (tests/test_sector_shapes_cpu.py).

@@ -1,6 +1,6 @@
-"""Block-structure problems for the sector path (grape_plan_setup.hpp find_sectors, grape_engine.hip
-symmetry_setup / setup_sector_head / decide_class) beyond the three Rydberg Hamiltonians: seeded random
-Hermitian blocks over the public Term / OperatorBasis* types, plain numpy.
+"""Block-structure problems for the sector path (grape_plan_setup.hpp find_sectors, grape_descriptor.hip
+symmetry_setup, grape_plan_build.hip setup_sector_head / decide_class) beyond the three Rydberg
+Hamiltonians: seeded random Hermitian blocks over the public Term / OperatorBasis* types, plain numpy.
 
 A problem is a tuple of component sizes (`comps`) plus `nfixed` levels no operator touches.  In canonical
 order the components' levels are consecutive and the fixed levels come last; a seeded permutation then

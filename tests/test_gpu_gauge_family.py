@@ -279,7 +279,7 @@ def test_latency_kernels_of_the_family(case, nt):
 def test_idle_dark_level_is_left_out_of_the_sectors(case):
     """With a detuning the dark state (|1r> - |r1>) / sqrt 2 has a diagonal entry: a level of its own that
     evolves by a phase.  Without projector weight that phase reaches neither F nor F_dx, and the sector layout
-    leaves the level out (grape_plan_setup.hpp find_sectors, grape_engine.hip idle_levels) -- as a third, padded 2-level sector it
+    leaves the level out (grape_plan_setup.hpp find_sectors, grape_descriptor.hip idle_levels) -- as a third, padded 2-level sector it
     kept the plan off the pair, merged and one-workgroup kernels.  Checked with the general head
     (GRAPE_OPT_GENERAL_HEAD assembles the whole U, zero on that level), and with weight on |1r> and |r1>: the
     level stays, a 1-level sector in the 2-level class, and the plan matches the oracle."""

@@ -170,7 +170,7 @@ def test_hidden_blocks_with_an_error_source():
 
 
 def test_hidden_twin_blocks():
-    """h3+22: the 2-level block of multiplicity two.  sector_info()["twin"] is what grape_engine.hip decide_class's
+    """h3+22: the 2-level block of multiplicity two.  sector_info()["twin"] is what grape_plan_build.hip decide_class's
     conditions give (a walking 2-level class of two sectors without error sources whose blocks of every H0
     operator are identical, bit for bit), and GRAPE_OPT_NO_TWIN changes no number beyond the tiers."""
     from robustgrape_amd.operators import OPT_NO_TWIN

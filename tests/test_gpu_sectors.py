@@ -237,7 +237,7 @@ def test_sectors_two_controls(monkeypatch):
     # the detuning control keeps the swap symmetry; the dark level (1r - r1)/sqrt2 now has a diagonal
     # (Nr = 1 there).  Weighted (|1r> and |r1> at 1/2 each: the rotated projector stays diagonal) it is a
     # 1-level sector in the 2-level class; without weight its phase reaches neither F nor a derivative
-    # and the sector layout leaves it out (grape_plan_setup.hpp find_sectors, grape_engine.hip idle_levels)
+    # and the sector layout leaves it out (grape_plan_setup.hpp find_sectors, grape_descriptor.hip idle_levels)
     W_dark = P.W_FULL9.copy()
     W_dark[6, 6] = W_dark[7, 7] = 0.5
     for W, layout in ((W_dark, ((3, 1), (2, 3))), (P.W_FULL9, P.FULL9_SYM)):

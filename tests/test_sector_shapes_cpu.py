@@ -110,7 +110,7 @@ def checker(tmp_path_factory):
 
 
 def _idle(fp):
-    """grape_engine.hip idle_levels restated: no projector weight and no target entry beside the diagonal."""
+    """grape_descriptor.hip idle_levels restated: no projector weight and no target entry beside the diagonal."""
     d = fp.unitary_problem.ndim
     W = np.asarray(fp.projector)
     if np.count_nonzero(W - np.diag(np.diag(W))):
