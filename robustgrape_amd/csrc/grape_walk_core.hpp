@@ -653,6 +653,12 @@ __device__ __forceinline__ WalkLane walk_lane(const DevProblem &P, const DevBatc
 #ifndef GRAPE_WALK_LADDER_CONTR  // ladder classes: the contraction grouped by charge difference
 #define GRAPE_WALK_LADDER_CONTR 1
 #endif
+#ifndef GRAPE_WIDE_TILE_FAST  // wide walks: full workgroup and full tile move x and F_dx by a uniform stride
+#define GRAPE_WIDE_TILE_FAST 1
+#endif
+#ifndef GRAPE_WIDE_STEP_FRAME  // wide forward walk, ladder charges: chi = D_k^dag psi walked through E~ itself
+#define GRAPE_WIDE_STEP_FRAME 1
+#endif
 template <int D, int NS>
 struct WalkCfg {
     static constexpr bool FENCE = D >= 4;        // per-column scheduling fences (register discipline)

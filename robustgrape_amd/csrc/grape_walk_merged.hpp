@@ -144,6 +144,40 @@ __device__ __forceinline__ void wide_step_fwd(const cd *Et, const GaugeN<D> (&gn
         for (int j = 0; j < D; ++j) psi[w][j] = t[j];
     }
 }
+// The forward walk in the step frame (ladder charges).  With D_k = diag(p_k^j) (gauge_phases_ladder: e_jm =
+// conj(p^(m-j)), so E_jm = p^j E~_jm p^-m and level j carries charge j), chi_k = D_k^dag psi_k obeys
+//   chi_k = E~ diag(dl^j) chi_{k-1},   dl = p_{k-1} conj(p_k)   (p before the first step: 1, chi = D_0^dag e_c after it)
+// so a step never forms E_k: the re-framing takes dl, dl^2 and D - 1 complex products per sector (20 VALU
+// instructions for one 3-level and one 2-level chain where E_k's formation takes 36), and E~'s entries are the
+// scalar operands of the 9 + 4 complex MACs themselves.  psi_N = D_{N-1} chi_N: one closing re-framing by
+// p_{N-1}.  The same quantity as wide_step_fwd, other roundings.
+template <int D, int NE, int DP>
+__device__ __forceinline__ void wide_reframe(const cd (&pw)[DP], cd (&chi)[NE][D]) {  // chi_j <- pw[j] chi_j, pw[0] = 1
+    static_assert(D <= DP, "powers up to the sector's highest charge");
+#pragma unroll
+    for (int w = 0; w < NE; ++w) {
+#pragma unroll
+        for (int j = 1; j < D; ++j) chi[w][j] = cmulf(chi[w][j], pw[j]);
+    }
+}
+template <int D, int NE>
+__device__ __forceinline__ void wide_step_frame(const cd *Et, cd (&chi)[NE][D]) {  // chi <- E~ chi
+#pragma unroll
+    for (int w = 0; w < NE; ++w) {
+        cptr<cd> g = as_constant(Et + w * D * D);  // (per-step scalar loads, as gauge_prop_lds<D, true>)
+        asm volatile("" : "+s"(g));
+        cd t[D];
+#pragma unroll
+        for (int j = 0; j < D; ++j) {
+            cd c = czero();
+#pragma unroll
+            for (int m = 0; m < D; ++m) cmac(c, chi[w][m], cload(g, j * D + m));
+            t[j] = c;
+        }
+#pragma unroll
+        for (int j = 0; j < D; ++j) chi[w][j] = t[j];
+    }
+}
 // the head's U block of one sector from psi_N: column c filled, the rest zero (the head's sums weight every
 // other entry with zero, which must not meet a NaN)
 template <int D>
@@ -170,6 +204,37 @@ __device__ __forceinline__ void wide_load_x(double (*tile)[kFdxTile + 1], const 
 #pragma unroll 4
     for (int r = r0; r < kWalkBlock; r += kStep) tile[r][j] = xc[(size_t)min(b0 + r, (long)nbe - 1) * nx];
 }
+// The same tile, and the gradient walk's F_dx flush, where nothing needs a clamp or a predicate: every row of the
+// workgroup is an evaluation (wide_group_full) and every slot of the tile a step (j0 + kFdxTile <= N_t).  Row
+// r0 + 8 i, slot j of the workgroup's tile is element (8 i nx) + (r0 nx + j) of the workgroup's first row at j0:
+// a uniform base stepped by a uniform stride, plus one per-lane offset (wide_tile_offset) formed once per kernel
+// -- one address add per element, where wide_load_x spends 11 VALU instructions per load and the predicated
+// flush 16 per store -- and the LDS addresses are immediates.  The same elements to and from the same slots.
+__device__ __forceinline__ bool wide_group_full(int nbe) {
+    return GRAPE_WIDE_TILE_FAST && ((long)blockIdx.x + 1) * kWalkBlock <= (long)nbe;
+}
+__device__ __forceinline__ unsigned wide_tile_offset(int nx) {
+    // in bytes, 32 bits: r0 < kWalkBlock / kFdxTile = 8 rows of nx <= 4097 doubles (the wide pass stops at
+    // N_t = 4096: wide_ok) and j < 16 make it at most 8 (7 x 4097 + 15) < 2^18
+    return (unsigned)((threadIdx.x / kFdxTile) * nx + threadIdx.x % kFdxTile) * (unsigned)sizeof(double);
+}
+__device__ __forceinline__ void wide_load_x_full(double (*tile)[kFdxTile + 1], const double *xb, int nx, unsigned off) {
+    constexpr int kStep = kWalkBlock / kFdxTile, kTrips = kWalkBlock / kStep;
+    const int j = threadIdx.x % kFdxTile, r0 = threadIdx.x / kFdxTile;
+    double v[kTrips];
+#pragma unroll
+    for (int i = 0; i < kTrips; ++i)
+        v[i] = *reinterpret_cast<const double *>(reinterpret_cast<const char *>(xb + (size_t)i * kStep * nx) + off);
+#pragma unroll
+    for (int i = 0; i < kTrips; ++i) tile[r0 + i * kStep][j] = v[i];
+}
+__device__ __forceinline__ void wide_flush_full(const double (*tile)[kFdxTile + 1], double *fb, int nx, unsigned off) {
+    constexpr int kStep = kWalkBlock / kFdxTile, kTrips = kWalkBlock / kStep;
+    const int j = threadIdx.x % kFdxTile, r0 = threadIdx.x / kFdxTile;
+#pragma unroll
+    for (int i = 0; i < kTrips; ++i)
+        *reinterpret_cast<double *>(reinterpret_cast<char *>(fb + (size_t)i * kStep * nx) + off) = tile[r0 + i * kStep][j];
+}
 template <int DA, bool TWB, bool LAD>
 __device__ __forceinline__ void wide_fwd_body(const DevProblem &PA, const DevBatch &BA, const DevProblem &PB,
                                               const DevBatch &BB) {
@@ -192,15 +257,31 @@ __device__ __forceinline__ void wide_fwd_body(const DevProblem &PA, const DevBat
 #pragma unroll
         for (int j = 0; j < 2; ++j) psiB[w][j] = cmake(j == PB.rank1_c[w] ? 1.0 : 0.0, 0.0);
     }
+    constexpr bool FRAME = LAD && GRAPE_WIDE_STEP_FRAME;  // (psi holds chi = D_k^dag psi: wide_step_frame)
+    cd pprev = cmake(1.0, 0.0);
     auto step = [&](double xk) {
         const cd p1 = gauge_cis_tab(PA.gauge_a * xk, ctab);
-        wide_step_fwd<DA, 1, LAD>(PA.gauge_Et, gA, p1, psiA);
-        wide_step_fwd<2, NEB, LAD>(PB.gauge_Et, gB, p1, psiB);
+        if constexpr (FRAME) {
+            cd pw[DA];
+            ladder_powers<DA>(cmulf(pprev, cconj(p1)), pw);
+            pprev = p1;
+            wide_reframe<DA, 1>(pw, psiA);
+            wide_reframe<2, NEB>(pw, psiB);
+            wide_step_frame<DA, 1>(PA.gauge_Et, psiA);
+            wide_step_frame<2, NEB>(PB.gauge_Et, psiB);
+        } else {
+            wide_step_fwd<DA, 1, LAD>(PA.gauge_Et, gA, p1, psiA);
+            wide_step_fwd<2, NEB, LAD>(PB.gauge_Et, gB, p1, psiB);
+        }
     };
+    const bool full = wide_group_full(L.nbe);
+    const unsigned off = wide_tile_offset(PA.nx);
+    const double *xb = BA.x + (size_t)blockIdx.x * kWalkBlock * PA.nx;  // the workgroup's first row
 #pragma unroll 1
     for (int j0 = 0; j0 < PA.Nt; j0 += kFdxTile) {
         const int nj = min(kFdxTile, PA.Nt - j0);
-        wide_load_x(xtile, BA.x, PA.nx, L.nbe, j0, PA.Nt);
+        if (full && j0 + kFdxTile <= PA.Nt) wide_load_x_full(xtile, xb + j0, PA.nx, off);
+        else wide_load_x(xtile, BA.x, PA.nx, L.nbe, j0, PA.Nt);
         __syncthreads();
         int t = 0;  // (unrolled by hand, as k_walk_fwd_m below)
 #pragma unroll 1
@@ -210,6 +291,12 @@ __device__ __forceinline__ void wide_fwd_body(const DevProblem &PA, const DevBat
         }
         if (t < nj) step(xtile[threadIdx.x][t]);
         __syncthreads();
+    }
+    if constexpr (FRAME) {  // psi_N = D_{N-1} chi_N: the head and the gradient walk read the lab frame
+        cd pw[DA];
+        ladder_powers<DA>(pprev, pw);
+        wide_reframe<DA, 1>(pw, psiA);
+        wide_reframe<2, NEB>(pw, psiB);
     }
     if (L.ok) {
         wide_store_u<DA>(BA.Ub + (size_t)L.be * DA * DA, cA, psiA[0]);
@@ -644,6 +731,9 @@ __device__ __forceinline__ void merged_r1_init(const cd *ca, size_t nbe, const c
 //   (grouped by charge difference with the rho weights and 1 / eps, as merged_step_grad_r1);
 //   phi_{k-1},j = conj(sum_r v_rj)
 // Per 3-level sector 36 FMA (psi) + 18 MUL + 18 FMA (v) + 24 FMA (T) + 12 ADD (phi): merged_step_grad_r1's count.
+// (The diagonal v_jj enter only phi's column sum; as a complex MAC onto the off-diagonal terms they are 10 F64
+// instructions fewer per step and lane, which bought 0.8 % of the gradient walk and nothing that the bench could
+// tell from its run-to-run spread: DESIGN.md 9.)
 template <int D, int NE, int NSEC, bool LAD>
 __device__ __forceinline__ double wide_step_grad(const cd *Et, const GaugeN<D> (&gn)[NE], cd p1, cd q, double inv_eps,
                                                  cd (&psi)[NSEC][D], cd (&phi)[NSEC][D]) {
@@ -778,19 +868,28 @@ __device__ __forceinline__ void wide_grad_body(const DevProblem &PA, const DevBa
     // holding the tile's controls (wide_load_x), each lane replaces x_k in its row by the step's F_dx value, and the
     // flush writes the rows out as k_walk_grad_m's does (slot t of the tile is step j0 + t).
     const int jlast = (PA.Nt - 1) / kFdxTile * kFdxTile;
+    const bool full = wide_group_full(L.nbe);
+    const unsigned off = wide_tile_offset(PA.nx);
+    const size_t row0 = (size_t)blockIdx.x * kWalkBlock * PA.nx;  // the workgroup's first row of x and of F_dx
 #pragma unroll 1
     for (int j0 = jlast; j0 >= 0; j0 -= kFdxTile) {
         const int nj = min(kFdxTile, PA.Nt - j0);
-        wide_load_x(ftile, BA.x, PA.nx, L.nbe, j0, PA.Nt);
+        const bool fast = full && j0 + kFdxTile <= PA.Nt;  // (workgroup-uniform)
+        if (fast) wide_load_x_full(ftile, BA.x + row0 + j0, PA.nx, off);
+        else wide_load_x(ftile, BA.x, PA.nx, L.nbe, j0, PA.Nt);
         __syncthreads();
 #pragma unroll 1
         for (int t = nj - 1; t >= 0; --t) ftile[threadIdx.x][t] = step(ftile[threadIdx.x][t]);
         __syncthreads();
-        const int j = threadIdx.x % kFdxTile;
+        if (fast) {
+            wide_flush_full(ftile, BA.Fdx + row0 + j0, PA.nx, off);
+        } else {
+            const int j = threadIdx.x % kFdxTile;
 #pragma unroll 1
-        for (int row = threadIdx.x / kFdxTile; row < kWalkBlock; row += kWalkBlock / kFdxTile) {
-            const int br = frow[row].x;  // (br < 0: past the last lane)
-            if (j < nj && br >= 0) BA.Fdx[(size_t)br * PA.nx + j0 + j] = ftile[row][j];
+            for (int row = threadIdx.x / kFdxTile; row < kWalkBlock; row += kWalkBlock / kFdxTile) {
+                const int br = frow[row].x;  // (br < 0: past the last lane)
+                if (j < nj && br >= 0) BA.Fdx[(size_t)br * PA.nx + j0 + j] = ftile[row][j];
+            }
         }
         __syncthreads();
     }
