@@ -29,7 +29,7 @@ PROJ = os.path.join(CSRC, "grape_projector.hip")
 WALK = os.path.join(CSRC, "grape_walk_inst.hip")
 EVAL1 = os.path.join(CSRC, "grape_eval1.hip")
 TILED = os.path.join(CSRC, "grape_tiled.hip")
-DIMS = list(range(2, 13))  # GRAPE_DIMS in grape_launch.hpp; GRAPE_MAX_SMALL_DIM = 12
+DIMS = list(range(2, 13))  # GRAPE_DIMS in grape_launch_api.hpp; GRAPE_MAX_SMALL_DIM = 12
 SOURCES = [ENGINE] + HOST + [INST, PROD, DENSE, UNITARY, LBFGS, PROJ, WALK, EVAL1, TILED]
 # every source and header of the library (an #include of a file that is not here would not reach source_id():
 # tests/test_capi_cpu.py checks the includes), the C ABI last

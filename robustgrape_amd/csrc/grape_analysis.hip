@@ -316,7 +316,7 @@ static int dense_expm_batch(int device, int ndim, int n, const double *A, double
     const size_t IMG = grape_dense::kImgDoubles;
     std::vector<double> h((size_t)n * IMG);
     for (int i = 0; i < n; ++i) to_dense_image(A + 2 * (size_t)i * ndim * ndim, ndim, h.data() + i * IMG);
-    grape_setup::DevicePool mem;
+    DevicePool mem;
     double *dA = nullptr, *dE = nullptr;
     int *dctrl = nullptr;
     if (mem.alloc(&dA, n * IMG) || mem.alloc(&dE, n * IMG) || mem.alloc(&dctrl, 8))
@@ -342,7 +342,7 @@ static int tiled_expm_batch(int ndim, int n, const double *A, double *E, int *st
     const size_t IMG = grape_tiled::image_doubles(ndim);
     std::vector<double> h((size_t)n * IMG);
     for (int i = 0; i < n; ++i) to_tiled_image(A + 2 * (size_t)i * ndim * ndim, ndim, h.data() + i * IMG);
-    grape_setup::DevicePool mem;
+    DevicePool mem;
     double *dA = nullptr, *dE = nullptr;
     int *dctl = nullptr, *dwords = nullptr, *h_smax = nullptr;
     grape_tiled::ExpSlab X{};
@@ -379,7 +379,7 @@ static int expm_batch(int device, int ndim, int n, const double *A, double *E, i
     if (ndim > GRAPE_MAX_DENSE_DIM) return tiled_expm_batch(ndim, n, A, E, stats);
     if (ndim > GRAPE_MAX_SMALL_DIM) return dense_expm_batch(device, ndim, n, A, E, stats, pivot);
     const size_t T = (size_t)ndim * ndim;
-    grape_setup::DevicePool mem;
+    DevicePool mem;
     cd *dA = nullptr, *dE = nullptr;
     int *dovf = nullptr, *dctrl = nullptr;
     if (mem.alloc(&dA, n * T) || mem.alloc(&dE, n * T) || mem.alloc(&dovf, (size_t)n) || mem.alloc(&dctrl, 8))

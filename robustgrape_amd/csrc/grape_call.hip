@@ -10,11 +10,6 @@
 
 #include "grape_plan.hpp"
 
-// instantiated in grape_inst.hip (the D = 4 translation unit)
-namespace grape_host {
-GRAPE_DECLARE_SCAN_PAIR(extern)
-}  // namespace grape_host
-
 using namespace grape_eng;
 
 namespace grape_eng {

@@ -27,6 +27,7 @@
 // grape_dense.hpp).
 #include "grape_dense.hpp"
 #include "grape_dense_api.hpp"
+#include "grape_projector_api.hpp"
 
 namespace grape_dense {
 

@@ -3,7 +3,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
-#include "grape_launch.hpp"
+#include "grape_launch_api.hpp"
 
 namespace grape_dense {
 

@@ -1,8 +1,9 @@
 // grape_descriptor.hip -- the pure host logic of plan creation: everything decided from the descriptor
 // alone, before (and without) a device.  Validation, the factor split, the Hermiticity checks, the projector
 // setup, idle levels, phase covariance (find_gauge), the symmetry-adapted view, and the route.
-// No kernel and no launch: the types come from grape.h, grape_plan_setup.hpp and grape_symmetry.hpp
-// (grape_descriptor.hpp), and one constant (grape_tiled::kMaxTerms) from grape_tiled_api.hpp.
+// No kernel, no launch and no HIP call: the types come from grape.h, grape_types.hpp, grape_plan_setup.hpp
+// and grape_symmetry.hpp (grape_descriptor.hpp).  The library's compiler builds it like every unit; it is also
+// plain C++17, which a host compiler builds without any HIP header (tests/c/descriptor_check.cpp links it).
 #include <algorithm>
 #include <cmath>
 #include <complex>
@@ -11,7 +12,6 @@
 #include <vector>
 
 #include "grape_descriptor.hpp"
-#include "grape_tiled_api.hpp"
 
 namespace grape_eng {
 

@@ -17,7 +17,7 @@ namespace grape_eng {
 int fail(int code, const std::string &msg);
 
 // (SectorClass, SectorSetup, pack_sectors, sector_cost and find_sectors -- the layout rule -- live in
-// grape_plan_setup.hpp, where tests/c/sectors_check.cpp runs them on the host.)
+// grape_plan_setup.hpp, where tests/c/descriptor_check.cpp runs them on the host.)
 using grape_setup::SectorClass;
 using grape_setup::SectorSetup;
 using grape_setup::find_sectors;
@@ -27,7 +27,7 @@ using grape_setup::sector_cost;
 // Product coefficients (grape.h GRAPE_OP_FACTOR).  A validated descriptor split once into the plain
 // descriptor every other piece of host logic sees -- operator terms only, err_term_offsets re-based, so
 // that nothing ever indexes ops[-1] -- and the factor slots of its H0 and error terms
-// (grape_kernels.hpp FactorTab: kMaxFactors slots per operator term, op = 1 live, 0 empty).  A descriptor
+// (grape_types.hpp FactorTab: kMaxFactors slots per operator term, op = 1 live, 0 empty).  A descriptor
 // without factor terms is passed through untouched (plain = *desc, the caller's own pointers).
 struct FactorSplit {
     bool any = false;

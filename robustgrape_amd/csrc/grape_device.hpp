@@ -35,12 +35,9 @@
 #include <stdint.h>
 
 #include "grape_pade_degree.hpp"
+#include "grape_types.hpp"  // cd
 
 namespace grape {
-
-struct cd {
-    double re, im;
-};
 
 __device__ __forceinline__ cd cmake(double r, double i) { cd z; z.re = r; z.im = i; return z; }
 __device__ __forceinline__ cd czero() { return cmake(0.0, 0.0); }

@@ -25,13 +25,6 @@
 
 #include "grape_plan.hpp"
 
-// instantiated in grape_inst.hip (one translation unit per dimension)
-namespace grape_host {
-#define GRAPE_EXTERN_DIM(d) GRAPE_DECLARE_DIM(d, extern)
-GRAPE_DIMS(GRAPE_EXTERN_DIM)
-#undef GRAPE_EXTERN_DIM
-}  // namespace grape_host
-
 static_assert(sizeof(Term) == sizeof(grape_term), "grape_term layout");
 
 namespace {
@@ -51,7 +44,8 @@ using grape_host::launch_pipeline;
 using grape_host::launch_expm_raw;
 using grape_host::set_lds_limits;
 
-// f(std::integral_constant<int, D>) for the instantiated dimension D (GRAPE_DIMS)
+// f(std::integral_constant<int, D>) for the dimension D (GRAPE_DIMS); the launch sequences called through it
+// are declared in grape_launch_api.hpp and instantiated in grape_inst.hip (one translation unit per dimension)
 template <class F>
 hipError_t dispatch_dim(int D, F &&f) {
     switch (D) {

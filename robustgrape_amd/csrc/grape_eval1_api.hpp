@@ -3,7 +3,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
-#include "grape_kernels.hpp"
+#include "grape_types.hpp"
 #include "grape_projector_api.hpp"
 
 namespace grape_eval1 {

@@ -1,13 +1,15 @@
-// grape_launch.hpp -- host-side launch sequences of the small-d engine, one
-// instantiation per compile-time dimension D.  Each D is compiled in its own
-// translation unit (grape_inst.hip with -DGRAPE_INST_DIM=D) so the build runs
-// in parallel; grape_engine.hip only sees the declarations (extern template).
+// grape_launch.hpp -- the bodies of the small-d engine's host-side launch sequences (declared in
+// grape_launch_api.hpp), templates on the compile-time dimension D.  Only the kernel units include this
+// header: grape_inst.hip (one translation unit per D, -DGRAPE_INST_DIM=D, so the build runs in parallel)
+// holds the explicit instantiations, grape_prod.hpp adds the product-coefficient launchers.  The host units
+// see the declarations alone.
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 
 #include "grape.h"
+#include "grape_launch_api.hpp"
 #include "grape_errpath.hpp"
 #include "grape_lane.hpp"
 #include "grape_walk_api.hpp"
@@ -15,34 +17,6 @@
 
 namespace grape_host {
 
-using grape::cd;
-using grape::DevBatch;
-using grape::DevProblem;
-
-// Scan workgroups: one per evaluation, W waves of row groups.  W = 8 (52 chunks
-// of L = 10 steps at d = 9, N_t = 512) has the shortest chains; W = 4 halves
-// the LDS and registers per block so two evaluations share a CU, which wins
-// once there are more evaluations than CUs (plan-time choice, see kScanWide).
-// Sector problems with many sub-evaluations per CU take W = 1: fewer chunks mean
-// fewer carries and per-chunk images to stream (C2 2.69 -> 2.80 M evals/s).
-constexpr int kScanWide = 8, kScanNarrow = 4, kScanTiny = 1;
-// Latency-bound calls (fewer sub-evaluations than CUs: single evaluations, C4's 32 restarts per
-// GPU, the optimiser's tail rounds) of the chunk-walk classes (<= kWalkMaxD levels, no error
-// sources) take 16-wave scans: twice the chunks of kScanWide, so each walk lane steps half as far
-// (L = 2 at 4 levels, L = 1 at 2 levels for N_t = 512).
-constexpr int kScanLatency = 16;
-
-// Lane-matrix exponentials (grape_lane.hpp k_expm_lane) for d <= kLaneMaxD (operator-basis
-// builders; closure tables keep k_expm_table); GRAPE_OPT_NO_LANE selects the row-group k_expm (A/B and
-// the bit-identity test).  Measured per instantiation (C2 sectors, 32 768 evaluations per pass,
-// rocprof, one box, profiles/r02/lane): S = 2 k_expm 1.057 -> 0.957 ms; S = 4 1.99 -> 2.26 ms (a
-// 4 x 4 complex matrix per lane is 64 VGPRs: 2 waves/SIMD), so d = 4 keeps the row groups.
-constexpr int kLaneMaxD = 3;
-// Sector stage 0 without error sources: propagators and chunk chains per lane up to kChainMaxD
-// (k_expm_chain_lane; a d = 4 variant measured 7.32 vs 3.81 ms and was dropped, grape_lane.hpp);
-// GRAPE_OPT_NO_CHAIN keeps k_expm + k_scan.  (Both are the fallbacks of the chunk walks,
-// grape_walk.hpp, which serve these classes by default.)
-constexpr int kChainMaxD = kLaneMaxD;
 template <int D>
 bool use_chain(const DevProblem &P, const DevBatch &B) {
     return D <= kChainMaxD && B.Htab == nullptr && !(P.opts & (GRAPE_OPT_NO_LANE | GRAPE_OPT_NO_CHAIN));
@@ -100,7 +74,7 @@ void launch_scan(const DevProblem &P, const DevBatch &B, hipStream_t st) {
 // the scans of two walk classes in one launch (D0 = 4 or 3, D1 = 2: the Rydberg layout), both at
 // width W: the latency scans (16 waves), and the throughput passes' one-wave scans, where the two
 // classes' short, under-filled scans then run side by side instead of one after the other
-template <int D0, int D1, int W = kScanLatency>
+template <int D0, int D1, int W>
 hipError_t launch_scan_pair(const DevProblem &P0, const DevBatch &B0, const DevProblem &P1, const DevBatch &B1,
                             hipStream_t st) {
     const size_t lds = std::max(scan_lds<D0>(W), scan_lds<D1>(W));
@@ -136,26 +110,6 @@ void launch_err_scan(const DevProblem &P, const DevBatch &B, hipStream_t st) {
         hipLaunchKernelGGL((grape::k_err_scan<D, kScanWide>), dim3(B.nb * P.ne), dim3(64 * kScanWide),
                            errscan_lds<D>(kScanWide), st, P, B);
 }
-
-// Product coefficients (grape_prod.hpp): plans with factor terms (F.h0 set) run k_expm_prod / k_expm_grad_prod
-// wherever the sequences below launch k_expm / k_expm_grad.  Defined and instantiated per dimension in
-// grape_prod_inst.hip; the launch geometry is that of the plain kernels.
-template <int D>
-hipError_t launch_expm_prod(bool err, const DevProblem &P, const DevBatch &B, const grape::FactorTab &F, hipStream_t st);
-template <int D>
-hipError_t launch_expm_grad_prod(const DevProblem &P, const DevBatch &B, const grape::FactorTab &F, hipStream_t st);
-
-// ---------------------------------------------------------------------------
-// dispatch helpers over the compile-time dimension
-// ---------------------------------------------------------------------------
-// Optional per-kernel event marks (profiling mode): fn(ctx, kernel, 0|1) around each launch.
-struct KMark {
-    void *ctx = nullptr;
-    void (*fn)(void *, int, int) = nullptr;
-    void operator()(int k, int phase) const {
-        if (fn) fn(ctx, k, phase);
-    }
-};
 
 template <int D>
 hipError_t launch_pipeline(const DevProblem &P, const DevBatch &B, const grape::FactorTab &F, hipStream_t st,
@@ -469,25 +423,5 @@ hipError_t set_lds_limits() {
     if (e == hipSuccess) e = set_lds_limits_w<D, kScanNarrow>();
     return e != hipSuccess ? e : set_lds_limits_w<D, kScanTiny>();
 }
-
-
-#define GRAPE_DIMS(X) X(2) X(3) X(4) X(5) X(6) X(7) X(8) X(9) X(10) X(11) X(12)
-// (the scan pair is instantiated in the D = 4 translation unit)
-#define GRAPE_DECLARE_SCAN_PAIR(EXT)                                                                       \
-    EXT template hipError_t launch_scan_pair<4, 2>(const DevProblem &, const DevBatch &, const DevProblem &, \
-                                                    const DevBatch &, hipStream_t);
-
-#define GRAPE_DECLARE_DIM(d, EXT)                                                                          \
-    EXT template hipError_t launch_pipeline<d>(const DevProblem &, const DevBatch &, const grape::FactorTab &, \
-                                               hipStream_t, const KMark &);                                   \
-    EXT template hipError_t launch_sector_stage<d>(int, const DevProblem &, const DevBatch &,                \
-                                                   const grape::FactorTab &, hipStream_t, const KMark &);     \
-    EXT template hipError_t launch_sector_reduce<d>(const DevProblem &, const DevBatch &, const grape::SecParts &, \
-                                                    int, hipStream_t, const KMark &);                         \
-    EXT template hipError_t launch_expm_raw<d>(const cd *, cd *, int, int *, int *, int *, int *, hipStream_t);  \
-    EXT template hipError_t set_lds_limits<d>();                                                          \
-    EXT template hipError_t launch_expm_variants<d>(const DevProblem &, const DevBatch &, const grape::FactorTab &, \
-                                                    hipStream_t);                                          \
-    EXT template hipError_t launch_expm_table<d>(const DevProblem &, const DevBatch &, hipStream_t);
 
 }  // namespace grape_host

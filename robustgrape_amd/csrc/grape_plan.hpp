@@ -1,9 +1,12 @@
 // grape_plan.hpp -- what the host units of the C ABI share: struct grape_plan, the error helpers, the
-// tuning constants and their -D knobs, and the declaration of every function that crosses a unit boundary
-// (namespace grape_eng).  The units: grape_engine.hip (errors, ids, fault handler, per-dimension dispatch,
-// plan lifetime and getters), grape_descriptor.hip (pure host logic on the descriptor),
-// grape_plan_build.hip (plan construction), grape_call.hip (the call path), grape_analysis.hip (the
-// single-evaluation analysis entry points).  Private to those units (not installed).
+// tuning constants and their -D knobs, the owner of a plan's device allocations (DevicePool), and the
+// declaration of every function that crosses a unit boundary (namespace grape_eng).  It includes the plain
+// types (grape_types.hpp) and the engines' API headers only: no kernel header and no launch body, so none of
+// these units can instantiate a kernel (tests/test_capi_cpu.py follows the includes).  The units:
+// grape_engine.hip (errors, ids, fault handler, per-dimension dispatch, plan lifetime and getters),
+// grape_descriptor.hip (pure host logic on the descriptor), grape_plan_build.hip (plan construction),
+// grape_call.hip (the call path), grape_analysis.hip (the single-evaluation analysis entry points).
+// Private to those units (not installed).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -11,7 +14,9 @@
 #include <vector>
 
 #include "grape.h"
-#include "grape_launch.hpp"
+#include "grape_launch_api.hpp"
+#include "grape_walk_api.hpp"
+#include "grape_projector_api.hpp"
 #include "grape_dense_api.hpp"
 #include "grape_tiled_api.hpp"
 #include "grape_unitary_api.hpp"
@@ -41,7 +46,7 @@ constexpr int kScanWide = grape_host::kScanWide, kScanNarrow = grape_host::kScan
 #endif
 constexpr int kForkMaxBatch = GRAPE_FORK_MAX_BATCH;
 // throughput passes of the Rydberg layout: both walk classes' one-wave scans in one launch
-// (grape_launch.hpp launch_scan_pair)
+// (grape_launch_api.hpp launch_scan_pair)
 // chunks of a phase-covariant throughput walk class: (64 / S) / this per scan wave.  2: C2
 // 26.4 -> 29.0 M evals/s (4: 27.7 M; one GPU call, gpurun_out A/B r5chunk)
 #ifndef GRAPE_GAUGE_CHUNK_DIV
@@ -72,6 +77,29 @@ constexpr int kPairMaxBatch = 64;
 constexpr int kEval1MaxBatch = GRAPE_EVAL1_MAX_BATCH;
 constexpr int kCtrlInts = 8;  // [0..1] single-eval counters, [2] status, [4..5] pipeline overflow counters
 
+// The one owner of a set of device allocations: alloc() hands out a buffer and remembers it,
+// release_all() -- at the latest the destructor, so a local pool is scoped scratch -- frees every one.
+// n == 0 allocates one element (a valid pointer for empty tables).
+struct DevicePool {
+    std::vector<void *> owned;
+    DevicePool() = default;
+    DevicePool(const DevicePool &) = delete;
+    DevicePool &operator=(const DevicePool &) = delete;
+    ~DevicePool() { release_all(); }
+    template <class T>
+    hipError_t alloc(T **out, size_t n) {
+        *out = nullptr;
+        if (n == 0) n = 1;
+        const hipError_t e = hipMalloc(reinterpret_cast<void **>(out), n * sizeof(T));
+        if (e == hipSuccess) owned.push_back(*out);
+        return e;
+    }
+    void release_all() {
+        for (void *b : owned) (void)hipFree(b);
+        owned.clear();
+    }
+};
+
 }  // namespace grape_eng
 
 struct grape_plan {
@@ -82,7 +110,7 @@ struct grape_plan {
     int *h_status = nullptr;           // pinned copy of the device status word
     DevProblem P{};
     int max_batch = 0;
-    grape_setup::DevicePool mem;  // owns every device buffer of the plan; the named pointers below are views
+    grape_eng::DevicePool mem;  // owns every device buffer of the plan; the named pointers below are views
     cd *d_ops = nullptr;
     cd *d_opsT = nullptr;
     Term *d_h0 = nullptr, *d_tgt = nullptr, *d_err = nullptr;
@@ -256,7 +284,7 @@ void to_dense_image(const double *src, int d, double *img);
 void from_dense_image(const double *img, int d, double *dst);
 void to_tiled_image(const double *src, int d, double *img);
 void from_tiled_image(const double *img, int d, double *dst);
-hipError_t alloc_exp_slab(grape_setup::DevicePool &mem, size_t items, size_t img, grape_tiled::ExpSlab &X,
+hipError_t alloc_exp_slab(DevicePool &mem, size_t items, size_t img, grape_tiled::ExpSlab &X,
                           double **extra, size_t n_extra);
 int create_dense(const grape_desc *desc, grape_plan *p, bool xadd_dep, const ProjectorSetup &ps, int n_err_terms);
 int create_tiled(const grape_desc *desc, grape_plan *p, const ProjectorSetup &ps);

@@ -261,7 +261,7 @@ constexpr size_t kTiledSlabItems = 1024;
 constexpr size_t kTiledSlabImages = 9;  // A, A^2, A^3, A^4, two Horner buffers, E', Q_{k-1} M'_c, Y^dag
 
 // slab of the exponential: `items` images in each of the six buffers, from one allocation
-hipError_t alloc_exp_slab(grape_setup::DevicePool &mem, size_t items, size_t img, grape_tiled::ExpSlab &X,
+hipError_t alloc_exp_slab(DevicePool &mem, size_t items, size_t img, grape_tiled::ExpSlab &X,
                                  double **extra, size_t n_extra) {
     double *base = nullptr;
     const hipError_t e = mem.alloc(&base, (6 + n_extra) * items * img);
@@ -692,7 +692,7 @@ static int alloc_class(PlanBuild &b, int cl, const std::vector<int> &gauge_n, co
 static int fill_gauge_table(grape_plan *p, int cl, bool err) {
     DevProblem &Pc = p->Ps[cl];
     const size_t nbm = (size_t)Pc.nsec * (err ? 1 + 2 * Pc.ne : 1), TS = (size_t)Pc.D * Pc.D;
-    grape_setup::DevicePool tmp;  // the fill's scratch
+    DevicePool tmp;  // the fill's scratch
     cd *scr = nullptr, *&gEt = p->sb[cl].gEt;
     if (p->mem.alloc(&gEt, nbm * TS) != hipSuccess || tmp.alloc(&scr, nbm * 2 * TS) != hipSuccess)
         return fail(GRAPE_ERR_ALLOC, err ? "device allocation failed (gauge error base)" : "device allocation failed (gauge base)");

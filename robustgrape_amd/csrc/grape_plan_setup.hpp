@@ -1,16 +1,12 @@
 // grape_plan_setup.hpp -- host-side pieces of plan construction (grape_plan_build.hip): the propagator
-// variant list, the owner of a plan's device allocations, the operator / projector tile layouts, and the
-// sector layout rule (find_sectors).
-// Host code only: no kernel and no launch.
+// variant list, the operator / projector tile layouts, and the sector layout rule (find_sectors).
+// Plain C++: no kernel, no launch and no HIP header, so host programs compile it (tests/c).
 #pragma once
-#include <hip/hip_runtime.h>
-
 #include <algorithm>
 #include <vector>
 
 #include "grape.h"
-#include "grape_kernels.hpp"
-#include "grape_projector_api.hpp"
+#include "grape_types.hpp"
 
 namespace grape_setup {
 
@@ -60,29 +56,6 @@ inline Variants build_variants(int np, int nxa, int ne, double eps, double eps2,
     }
     return V;
 }
-
-// The one owner of a set of device allocations: alloc() hands out a buffer and remembers it,
-// release_all() -- at the latest the destructor, so a local pool is scoped scratch -- frees every one.
-// n == 0 allocates one element (a valid pointer for empty tables).
-struct DevicePool {
-    std::vector<void *> owned;
-    DevicePool() = default;
-    DevicePool(const DevicePool &) = delete;
-    DevicePool &operator=(const DevicePool &) = delete;
-    ~DevicePool() { release_all(); }
-    template <class T>
-    hipError_t alloc(T **out, size_t n) {
-        *out = nullptr;
-        if (n == 0) n = 1;
-        const hipError_t e = hipMalloc(reinterpret_cast<void **>(out), n * sizeof(T));
-        if (e == hipSuccess) owned.push_back(*out);
-        return e;
-    }
-    void release_all() {
-        for (void *b : owned) (void)hipFree(b);
-        owned.clear();
-    }
-};
 
 // Operator basis: column-major interleaved d x d matrices -> row-major cd tiles (row builds) and
 // column-major ones (the exp kernels build columns; col may be null).  With sidx ([nsec][S]: the level

@@ -30,6 +30,7 @@
 // These heads run once per evaluation (per error source), not per time step: plain
 // thread-per-element products over row-major d x d scratch matrices in HBM (L2-resident),
 // one 256-thread workgroup per evaluation, any d <= 64.
+#include "grape_kernels.hpp"
 #include "grape_projector_api.hpp"
 
 namespace grape_proj {

@@ -4,7 +4,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
-#include "grape_kernels.hpp"
+#include "grape_types.hpp"
 
 namespace grape_proj {
 
@@ -62,7 +62,7 @@ struct SectorHead {
                               // weighted level c and Ub holds column c only; instead of the M blocks the head
                               // writes alpha per sector, Msec[c] = [nb * nsec], where row c of M is alpha U_c.
 };
-constexpr int kSectorLds = 2048;  // complex elements of LDS for the sector blocks M_ww (nsec * S * S)
+// (kSectorLds, the LDS capacity for the sector blocks M_ww: grape_types.hpp)
 hipError_t launch_sector_head(const SectorHead &H, int nb, hipStream_t st);
 // one wave per (evaluation, error source): F_d2err, M_e blocks, F_d2err_dx_add target part
 hipError_t launch_sector_err_head(const SectorHead &H, int nb, hipStream_t st);

@@ -4,7 +4,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
-#include "grape_launch.hpp"
+#include "grape_launch_api.hpp"
 
 namespace grape_tiled {
 
@@ -13,7 +13,7 @@ inline int padded_dim(int d) { return 16 * ((d + 15) / 16); }
 // doubles of one image: re plane then im plane, row-major Pd x Pd, zero padding
 inline size_t image_doubles(int d) { return 2 * (size_t)padded_dim(d) * padded_dim(d); }
 
-constexpr int kMaxTerms = 256;  // H0 / target terms a tiled plan serves (coefficients staged in LDS)
+// (kMaxTerms, the H0 / target terms a tiled plan serves: grape_types.hpp)
 
 // Scalars and term tables are shared with the other engines (DevProblem: ops / opsT / vs unused
 // here); the operator basis is stored as images.

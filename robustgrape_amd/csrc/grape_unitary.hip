@@ -24,6 +24,7 @@
 // ones over d x d tiles: staged in LDS for d <= kMaxD (one workgroup per item), and
 // for the dense engine's 12 < d <= 64 in global scratch (kTiles tiles per workgroup,
 // kResident workgroups striding over the items, the operands L2-resident).
+#include "grape_kernels.hpp"
 #include "grape_unitary_api.hpp"
 
 #include <algorithm>

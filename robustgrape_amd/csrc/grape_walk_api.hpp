@@ -3,9 +3,9 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "grape_types.hpp"
+
 namespace grape {
-struct DevProblem;
-struct DevBatch;
 constexpr int kWalkMaxD = 4;  // sector classes of at most this many levels take the walks
 constexpr int kWalkMaxNpA = 2;  // ... with at most this many controls per step and x_add entries
 constexpr int kGaugeMaxE = 8;  // error sources of a phase-covariant image walk (grape_walk.hpp k_walk_img_gauge)

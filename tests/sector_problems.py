@@ -15,7 +15,7 @@ contiguous and the components interleave.
 with dt = 1 and every H0 / Herror operator scaled by one factor so that max_k |dt H0|_1 over the problem's
 own controls (block_x) is `step_norm`.
 
-CASES is the layout table the tests pin (tests/test_sector_shapes_cpu.py through tests/c/sectors_check.cpp
+CASES is the layout table the tests pin (tests/test_sector_shapes_cpu.py through tests/c/descriptor_check.cpp
 on the host, tests/test_gpu_sector_shapes.py on the device): name -> (block_problem arguments, layout with
 GRAPE_OPT_NO_SYMMETRY in GrapePlan.sectors() notation)."""
 from __future__ import annotations

@@ -106,6 +106,57 @@ def test_walk_piece_compiles_on_its_own(piece, tmp_path):
     assert r.returncode == 0, r.stderr[-4000:]
 
 
+PLAIN_HEADERS = ["grape_types.hpp", "grape_plan_setup.hpp", "grape_descriptor.hpp"]  # no HIP: plain C++17
+API_HEADERS = ["grape_launch_api.hpp", "grape_projector_api.hpp", "grape_unitary_api.hpp", "grape_eval1_api.hpp",
+               "grape_dense_api.hpp", "grape_tiled_api.hpp", "grape_walk_api.hpp"]
+
+
+@pytest.mark.parametrize("header", PLAIN_HEADERS + API_HEADERS)
+def test_api_header_compiles_on_its_own(header, tmp_path):
+    """Every header the host units see includes what it uses: alone in a unit it passes the front end, the plain
+    ones as C++ without offload flags (the HIP headers are never read), the others with the library's flags."""
+    import subprocess
+    from robustgrape_amd import build
+    plain = header in PLAIN_HEADERS
+    unit = tmp_path / ("piece.cpp" if plain else "piece.hip")
+    unit.write_text(f'#include "{header}"\n')
+    cmd = [build.HIPCC] + build.FLAGS
+    if plain:  # the host compiler: no HIP header is on its include path
+        import shutil
+        cmd = [os.environ.get("CXX") or shutil.which("g++") or "/opt/rocm/llvm/bin/clang++", "-std=c++17", "-x", "c++"]
+        cmd += [f for f in build.FLAGS if f.startswith("-I")]
+    r = subprocess.run(cmd + ["-fsyntax-only", str(unit)], capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr[-4000:]
+
+
+def _includes(name, seen):
+    """Every file that csrc/<name> includes with `#include "..."`, directly or through another header."""
+    from robustgrape_amd import build
+    path = os.path.join(build.CSRC, name)
+    if name in seen or not os.path.isfile(path):  # (grape.h lives under include/ and includes no project file)
+        return seen
+    seen.add(name)
+    for inc in re.findall(r'^\s*#\s*include\s+"([^"]+)"', open(path).read(), re.M):
+        _includes(inc, seen)
+    return seen
+
+
+def test_host_units_include_no_kernel_header():
+    """The five host units of the C ABI, and every header they are built from, reach no kernel header and no
+    launch body: a launch sequence they call is declared only (grape_launch_api.hpp), so one that no kernel unit
+    instantiates fails to link instead of being compiled into a host unit unnoticed."""
+    from robustgrape_amd import build
+    roots = [os.path.basename(s) for s in [build.ENGINE] + build.HOST]
+    roots += sorted(f for f in os.listdir(build.CSRC) if f.endswith("_api.hpp"))
+    roots += ["grape_plan.hpp", "grape_plan_setup.hpp", "grape_descriptor.hpp"]
+    assert len(roots) == 5 + len(API_HEADERS) + 3
+    banned = re.compile(r"grape_(kernels|device|launch|errpath|lane|walk|walk_(?!api\.)\w+)\.hpp")
+    for root in roots:
+        reached = _includes(root, set()) - {root}
+        assert not [h for h in reached if banned.fullmatch(h)], (root, sorted(reached))
+    assert "grape_types.hpp" in _includes("grape_plan.hpp", set())  # the walk follows the includes
+
+
 def test_descriptor_packing_roundtrip():
     """The ctypes descriptor reproduces the operator basis (column-major, interleaved)."""
     from robustgrape_amd.operators import DescriptorBuffers

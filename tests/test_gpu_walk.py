@@ -336,6 +336,35 @@ def test_pair_launches_bitwise(name, fp, nparam, sym, gauge):
         _check(f"pair_full9_{'gauge' if gauge else 'exp'}", b0[0][0], b0[1][0], F0, g0, True)
 
 
+@pytest.mark.parametrize("sym", [True, False])
+def test_one_wave_pair_scan_bitwise(sym):
+    """Throughput calls of a two-class walk plan that is neither merged (GRAPE_OPT_NO_MERGE) nor forked (more
+    evaluations than kForkMaxBatch = 4 096) scan both classes' chunk totals in one launch of one-wave workgroups
+    (k_scan_pair<3 or 4, 2, 1>).  The same rows in calls of at most 4 096 evaluations fork: one k_scan<S, 1> per
+    class, the same scan body on the same totals, so F and F_dx agree bit for bit.  The k_scan launch counts of
+    the profiling marks tell which path each call took."""
+    from robustgrape_amd.operators import OPT_NO_MERGE, OPT_NO_SYMMETRY
+    n, nt = 4097, 16
+    f = P.full9_problem(nt)
+    X = np.random.default_rng(31).uniform(0, 2 * np.pi, size=(n, nt + 1))
+    X[::2, :nt] *= 0.001
+    pl = _plan(f, n, OPT_NO_MERGE | (0 if sym else OPT_NO_SYMMETRY))
+    try:
+        assert pl.sectors() == (P.FULL9_SYM if sym else P.FULL9_PERM)
+        pl.set_profiling(True)
+        F, G = pl.fidelity_grad(X)[:2]
+        scans = pl.kernel_times(reset=True)["k_scan"][1]
+        parts = [pl.fidelity_grad(X[:n - 1])[:2], pl.fidelity_grad(X[n - 1:])[:2]]
+        scans_forked = pl.kernel_times()["k_scan"][1]
+    finally:
+        pl.close()
+    # (the sector head is timed in the k_scan slot too) one pair scan + the head; two calls of a scan per class + the head
+    assert (scans, scans_forked) == (1 + 1, 2 * (2 + 1))
+    assert np.all(np.isfinite(G)) and np.all(np.max(np.abs(G), axis=1) > 0)
+    assert np.array_equal(F, np.concatenate([p[0] for p in parts]))
+    assert np.array_equal(G, np.concatenate([p[1] for p in parts]))
+
+
 @pytest.mark.parametrize("gauge", [True, False])
 @pytest.mark.parametrize("nb,max_batch", [(300, 300), (3, 8)])
 def test_twin_sectors_bitwise(nb, max_batch, gauge):

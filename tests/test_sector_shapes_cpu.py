@@ -2,9 +2,12 @@
 
 * the generator does what it says: the union sparsity pattern has exactly the requested components, the fixed
   levels are fixed, the closure form returns the operator-basis matrices, scattering the labels changes no F;
-* the layout table (sector_problems.CASES) and two refusals, through grape_plan_setup.hpp find_sectors itself:
-  tests/c/sectors_check.cpp is built as host code under AddressSanitizer and UBSan and run as a child process
-  (as tests/test_variants_cpu.py does), with levels ascending inside each component and padding slots last;
+* the layout table (sector_problems.CASES) and two refusals, through the library's own host logic: validate_desc,
+  choose_route, setup_projector and idle_levels of grape_descriptor.hip, then grape_plan_setup.hpp find_sectors.
+  tests/c/descriptor_check.cpp and grape_descriptor.hip are built as plain C++ by the host compiler under
+  AddressSanitizer and UBSan and run as a child process, with levels ascending inside each component and padding
+  slots last; the idle mask of idle_levels equals its restatement here (_idle) in every case;
+* malformed descriptors: validate_desc returns an error code, with nothing for the sanitizers to report;
 * the hidden-block cases: grape_symmetry_basis block-diagonalises them with the expected block sizes;
 * the condition of tests/test_gpu_sector_shapes.py's comparison against the exact evaluator: the oracle's own
   distance from the exact F_dx lies inside fd_tier for every case, so the device test leans on no noisy checker."""
@@ -20,8 +23,9 @@ from tests import sector_problems as SP
 from tests.test_symmetry_cpu import _basis, _check_block_diagonal, _used_ops
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+CXX = os.environ.get("CXX") or shutil.which("g++") or "/opt/rocm/llvm/bin/clang++"
 OPT_NO_SYMMETRY = 1024
+ERR_INVALID = -1  # GRAPE_ERR_INVALID
 NT = 5
 
 
@@ -100,12 +104,13 @@ def test_scattering_the_labels_changes_no_fidelity(name):
 # ---------------------------------------------------------------------------------------------------------------
 @pytest.fixture(scope="module")
 def checker(tmp_path_factory):
-    if not os.path.exists(HIPCC) and not shutil.which("hipcc"):
-        pytest.skip("no hipcc")
-    exe = str(tmp_path_factory.mktemp("sectors") / "sectors_check")
-    subprocess.run([HIPCC, "-O1", "-std=c++17", "-Xarch_host", "-fsanitize=address,undefined",
-                    "-I" + os.path.join(ROOT, "robustgrape_amd", "csrc"), "-I" + os.path.join(ROOT, "include"),
-                    os.path.join(ROOT, "tests", "c", "sectors_check.cpp"), "-o", exe], check=True, capture_output=True)
+    if not shutil.which(CXX):
+        pytest.skip("no host C++ compiler")
+    exe = str(tmp_path_factory.mktemp("sectors") / "descriptor_check")
+    csrc = os.path.join(ROOT, "robustgrape_amd", "csrc")
+    subprocess.run([CXX, "-O1", "-std=c++17", "-fsanitize=address,undefined", "-I" + csrc,
+                    "-I" + os.path.join(ROOT, "include"), "-x", "c++", os.path.join(ROOT, "tests", "c", "descriptor_check.cpp"),
+                    os.path.join(csrc, "grape_descriptor.hip"), "-o", exe], check=True, capture_output=True)
     return exe
 
 
@@ -122,8 +127,8 @@ def _idle(fp):
     return idle
 
 
-def _layout(checker, fp, tmp_path, options=OPT_NO_SYMMETRY):
-    """find_sectors on the problem's operators: ([(S, nsec, sidx (nsec, S))], fixed levels)."""
+def _run(checker, fp, tmp_path, options, broken="ok"):
+    """tests/c/descriptor_check.cpp on the problem: its output lines."""
     up = fp.unitary_problem
     d = up.ndim
     ops, index = [], {}
@@ -135,9 +140,16 @@ def _layout(checker, fp, tmp_path, options=OPT_NO_SYMMETRY):
         return index[id(m)]
     h0 = [op_id(t.op) for t in up.H0.terms]
     errs = [[op_id(t.op) for t in es.Herror.terms] for es in up.error_sources]
+    tgt = [op_id(t.op) for t in fp.target_unitary.terms]
     lines = [f"{d} {len(ops)} {len(h0)} {len(errs)} {options}", " ".join(map(str, h0))]
-    lines += [" ".join(map(str, [len(e)] + e)) for e in errs]
-    lines.append(" ".join(str(int(v)) for v in _idle(fp)))
+    lines += [" ".join(map(str, [len(e)] + e)) for e in errs + [tgt]]
+    lines.append(f"{up.ntimes} 1 {up.nb_additional_param}")
+    W = np.asarray(fp.projector, np.complex128)
+    if np.count_nonzero(W - np.diag(np.diag(W))) or np.any(np.diag(W).imag):
+        lines.append("full " + " ".join(f"{float(v.real)!r} {float(v.imag)!r}" for v in W.flatten(order="F")))
+    else:
+        lines.append("diag " + " ".join(repr(float(v.real)) for v in np.diag(W)))
+    lines.append(broken)
     for o in ops:
         nz = np.argwhere(o != 0)
         lines.append(str(len(nz)))
@@ -146,7 +158,16 @@ def _layout(checker, fp, tmp_path, options=OPT_NO_SYMMETRY):
     path.write_text("\n".join(lines) + "\n")
     run = subprocess.run([checker, str(path)], check=True, capture_output=True, text=True)
     assert run.stderr == ""  # no sanitizer report
-    out = run.stdout.splitlines()
+    return run.stdout.splitlines()
+
+
+def _layout(checker, fp, tmp_path, options=OPT_NO_SYMMETRY):
+    """find_sectors on the problem's operators, with the idle levels of idle_levels: ([(S, nsec, sidx (nsec, S))],
+    fixed levels)."""
+    out = _run(checker, fp, tmp_path, options)
+    assert out[0].split()[:2] == ["validate", "0"] and out[1] == "route 0"
+    assert [int(v) for v in out[2].split()] == _idle(fp).astype(int).tolist()  # idle_levels and its restatement
+    out = out[3:]
     ncls, nfixed = (int(v) for v in out[0].split())
     cls = []
     for c in range(ncls):
@@ -222,6 +243,17 @@ def test_layout_refusals(checker, tmp_path):
     assert [(S, n) for S, n, _ in cls] == [(2, 2)]
     # GRAPE_OPT_NO_SECTORS
     assert _layout(checker, SP.case_problem("c431", NT), tmp_path, options=1) == ([], [])
+
+
+@pytest.mark.parametrize("broken, message", [("op", "H0: op out of range"),
+                                             ("offsets", "each error source needs at least one term")])
+def test_malformed_descriptors_are_refused(checker, broken, message, tmp_path):
+    """A term whose op is n_ops, and err_term_offsets that decrease: validate_desc claims both and returns
+    GRAPE_ERR_INVALID before anything indexes with them.  (nerr > 0 with a null err_terms is not among its claims:
+    it checks err_term_offsets alone, so that case is not run.)"""
+    fp = SP.case_problem("c431", NT, nerr=2)
+    assert _run(checker, fp, tmp_path, OPT_NO_SYMMETRY)[0].split()[:2] == ["validate", "0"]
+    assert _run(checker, fp, tmp_path, OPT_NO_SYMMETRY, broken) == [f"validate {ERR_INVALID} {message}"]
 
 
 # ---------------------------------------------------------------------------------------------------------------

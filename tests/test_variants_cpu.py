@@ -1,8 +1,8 @@
 """The propagator-variant layout (robustgrape_amd/csrc/grape_plan_setup.hpp build_variants) on the host.
 
 The kernels index the list through off_dx / off_dxa / off_dx2 / off_err / err_stride, so a slip gives wrong
-gradients and no error.  tests/c/variants_check.cpp is built with hipcc (the types live in a header that
-includes HIP) as host code under AddressSanitizer and UBSan and run as an ordinary child process.
+gradients and no error.  tests/c/variants_check.cpp is built with hipcc as host code under AddressSanitizer
+and UBSan and run as an ordinary child process (grape_plan_setup.hpp is plain C++ by now: a host compiler would do).
 
 The expected tables restate, by reading them, the three lists that plan construction wrote out by hand
 before the builder existed (grape_engine.hip at commit 5c26d4f):
