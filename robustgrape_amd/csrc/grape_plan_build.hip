@@ -541,15 +541,15 @@ static int setup_sector_head(PlanBuild &b) {
     H.ncls = (int)ss.cls.size();
     H.fixed = p->d_fixed;
     H.nfixed = (int)ss.fixed.size();
-    // diagonal projector and target, classes of <= 4 levels: the one-thread-per-evaluation head
-    // (grape_projector.hip k_sec_head_diag)
+    // diagonal projector and target, classes of <= 4 levels, at most kDiagMaxRows sector rows: the
+    // row-parallel heads (grape_projector.hip k_sec_head_diag, k_sec_err_head_rows)
     H.diag = !sps.general && !b.rt.tables && !(P.opts & GRAPE_OPT_GENERAL_HEAD);
-    int rows = 0;  // the row-parallel head's lanes per evaluation (grape_projector.hip diag_group)
+    int rows = 0;  // the heads' lanes per evaluation (grape_projector.hip diag_group)
     for (const SectorClass &sc : ss.cls) {
         H.diag = H.diag && sc.S <= 4;
         rows += sc.nsec * sc.S;
     }
-    H.diag = H.diag && rows <= 32;
+    H.diag = H.diag && rows <= grape_proj::kDiagMaxRows;
     for (int k = 0; H.diag && k < desc->n_target_terms; ++k) {
         const double *op = b.sdesc.ops + 2 * (size_t)desc->target_terms[k].op * D * D;
         for (int i = 0; i < D; ++i)

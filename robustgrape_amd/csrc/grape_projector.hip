@@ -28,8 +28,12 @@
 // (for A = diag(w), B = diag(w != 0) these are the hot kernels' formulas).
 //
 // These heads run once per evaluation (per error source), not per time step: plain
-// thread-per-element products over row-major d x d scratch matrices in HBM (L2-resident),
-// one 256-thread workgroup per evaluation, any d <= 64.
+// thread-per-element products over row-major d x d matrices.  Each formula has two kernels with
+// the same sequence of products and sums: k_proj_fid / k_proj_err, one 256-thread workgroup per
+// evaluation over scratch matrices in HBM (L2-resident), any d <= 64; and the sector heads
+// k_sec_head / k_sec_err_head, one wave over matrices in LDS, d <= 12 (a change to M, M_e or a
+// target part goes into both).  A diagonal projector and target on sectors take the specialised
+// heads further down instead.
 #include "grape_kernels.hpp"
 #include "grape_projector_api.hpp"
 
@@ -38,18 +42,13 @@ namespace grape_proj {
 namespace {
 
 using grape::cd;
+using grape::cadd, grape::csub, grape::cscale, grape::cmul, grape::cconj;  // grape_device.hpp: plain, unfused
 constexpr int BLOCK = 256;
-
-__device__ __forceinline__ cd p_add(cd a, cd b) { return cd{a.re + b.re, a.im + b.im}; }
-__device__ __forceinline__ cd p_sub(cd a, cd b) { return cd{a.re - b.re, a.im - b.im}; }
-__device__ __forceinline__ cd p_scale(double s, cd a) { return cd{s * a.re, s * a.im}; }
-__device__ __forceinline__ cd p_mul(cd a, cd b) { return cd{a.re * b.re - a.im * b.im, a.re * b.im + a.im * b.re}; }
-__device__ __forceinline__ cd p_conj(cd a) { return cd{a.re, -a.im}; }
 
 // op(X)(i, l): X row-major, op = N (X) or H (X^dagger)
 template <bool H>
 __device__ __forceinline__ cd el(const cd *X, int D, int i, int l) {
-    return H ? p_conj(X[(size_t)l * D + i]) : X[(size_t)i * D + l];
+    return H ? cconj(X[(size_t)l * D + i]) : X[(size_t)i * D + l];
 }
 
 // C = op(A) op(B); C must not alias A or B.  Ends with a workgroup barrier.
@@ -58,7 +57,7 @@ __device__ void bmm(cd *C, const cd *A, const cd *B, int D) {
     for (int t = threadIdx.x; t < D * D; t += blockDim.x) {
         const int i = t / D, j = t % D;
         cd s{0.0, 0.0};
-        for (int l = 0; l < D; ++l) s = p_add(s, p_mul(el<HA>(A, D, i, l), el<HB>(B, D, l, j)));
+        for (int l = 0; l < D; ++l) s = cadd(s, cmul(el<HA>(A, D, i, l), el<HB>(B, D, l, j)));
         C[t] = s;
     }
     __syncthreads();
@@ -132,16 +131,29 @@ __device__ void store_image(double *img, const cd *src, int D) {
     __syncthreads();
 }
 
+// the target's perturbation: none, or x_add[q] + eps (the forward differences of the x_add target parts)
+__device__ __forceinline__ grape::Pert no_pert() {
+    grape::Pert p;
+    p.var = -1;
+    p.index = 0;
+    p.delta = 0.0;
+    return p;
+}
+__device__ __forceinline__ grape::Pert xadd_pert(const grape::DevProblem &P, int q) {
+    grape::Pert p;
+    p.var = grape::VAR_XADD;
+    p.index = q;
+    p.delta = P.eps;
+    return p;
+}
+
 // U0(x_add [+ eps e_q]) row-major: from the target terms over the row-major operator basis,
 // or (closure fallback) from the host-evaluated table (column-major, slot 0 / 1 + q)
 __device__ void build_target(const grape::DevProblem &P, const cd *U0tab, int b, const double *xb, int slot,
                              cd *dst) {
     const int D = P.D;
     const double *xadd = xb + (size_t)P.np * P.Nt;
-    grape::Pert pp;
-    pp.var = slot > 0 ? grape::VAR_XADD : -1;
-    pp.index = slot > 0 ? slot - 1 : 0;
-    pp.delta = slot > 0 ? P.eps : 0.0;
+    const grape::Pert pp = slot > 0 ? xadd_pert(P, slot - 1) : no_pert();
     for (int t = threadIdx.x; t < D * D; t += blockDim.x) {
         const int i = t / D, j = t % D;
         if (U0tab) {
@@ -151,7 +163,7 @@ __device__ void build_target(const grape::DevProblem &P, const cd *U0tab, int b,
         cd h{0.0, 0.0};
         for (int q = 0; q < P.n_tgt; ++q) {
             const grape::Term tm = P.tgt[q];
-            h = p_add(h, p_mul(grape::term_coef(tm, 1, xb, xadd, pp), P.ops[(size_t)tm.op * D * D + t]));
+            h = cadd(h, cmul(grape::term_coef(tm, 1, xb, xadd, pp), P.ops[(size_t)tm.op * D * D + t]));
         }
         dst[t] = h;
     }
@@ -192,13 +204,13 @@ __global__ __launch_bounds__(BLOCK) void k_proj_fid(Heads H) {
     bmm<true, false>(T1, X, K, D);
     bmm<true, false>(T2, Bm, T1, D);
     for (int t = threadIdx.x; t < (int)T; t += blockDim.x) {
-        const cd ct = p_mul(cd{tau.re, -tau.im}, X[t]);
-        M[t] = p_scale(1.0 / P.DD, p_add(p_add(M[t], T2[t]), p_scale(2.0, ct)));
+        const cd ct = cmul(cd{tau.re, -tau.im}, X[t]);
+        M[t] = cscale(1.0 / P.DD, cadd(cadd(M[t], T2[t]), cscale(2.0, ct)));
     }
     __syncthreads();
     for (int q = 0; q < P.na; ++q) {  // target part of F_dx_add
         build_target(P, H.U0tab, b, xb, 1 + q, T1);
-        for (int t = threadIdx.x; t < (int)T; t += blockDim.x) T1[t] = p_scale(P.inv_eps, p_sub(T1[t], U0[t]));
+        for (int t = threadIdx.x; t < (int)T; t += blockDim.x) T1[t] = cscale(P.inv_eps, csub(T1[t], U0[t]));
         __syncthreads();
         bmm<true, false>(T2, T1, U, D);   // Kd
         bmm<false, false>(T1, A, T2, D);  // A Kd
@@ -264,19 +276,19 @@ __global__ __launch_bounds__(BLOCK) void k_proj_err(Heads H) {
     bmm<true, false>(T1, Xe, K, D);
     bmm<true, false>(T2, Bm, T1, D);
     for (int t = threadIdx.x; t < (int)T; t += blockDim.x) {
-        M[t] = p_add(p_add(M[t], T2[t]), p_scale(2.0, p_mul(cd{te.re, -te.im}, X[t])));
+        M[t] = cadd(cadd(M[t], T2[t]), cscale(2.0, cmul(cd{te.re, -te.im}, X[t])));
         const int i = t / D, j = t % D;
-        T2[t] = p_add(A[t], p_conj(A[(size_t)j * D + i]));  // A + A^dagger
+        T2[t] = cadd(A[t], cconj(A[(size_t)j * D + i]));  // A + A^dagger
     }
     __syncthreads();
     bmm<true, false>(T1, Ue, U, D);
     bmm<false, false>(T3, T2, T1, D);
     for (int t = threadIdx.x; t < (int)T; t += blockDim.x)
-        M[t] = p_scale(2.0 / P.DD, p_sub(M[t], p_scale(1.0 + P.Dtr, T3[t])));
+        M[t] = cscale(2.0 / P.DD, csub(M[t], cscale(1.0 + P.Dtr, T3[t])));
     __syncthreads();
     for (int q = 0; q < P.na; ++q) {  // target part of F_d2err_dx_add
         build_target(P, H.U0tab, b, xb, 1 + q, T1);
-        for (int t = threadIdx.x; t < (int)T; t += blockDim.x) T1[t] = p_scale(P.inv_eps, p_sub(T1[t], U0[t]));
+        for (int t = threadIdx.x; t < (int)T; t += blockDim.x) T1[t] = cscale(P.inv_eps, csub(T1[t], U0[t]));
         __syncthreads();
         bmm<true, false>(T2, T1, Ue, D);  // Kde
         bmm<false, false>(T1, A, T2, D);
@@ -344,13 +356,13 @@ __global__ __launch_bounds__(SEC_BLOCK) void k_sec_head(SectorHead H) {
     bmm<true, false>(T1, X, K, D);
     bmm<true, false>(T2, Bm, T1, D);
     for (int t = threadIdx.x; t < (int)T; t += blockDim.x) {
-        const cd ct = p_mul(cd{tau.re, -tau.im}, X[t]);
-        M[t] = p_scale(1.0 / P.DD, p_add(p_add(M[t], T2[t]), p_scale(2.0, ct)));
+        const cd ct = cmul(cd{tau.re, -tau.im}, X[t]);
+        M[t] = cscale(1.0 / P.DD, cadd(cadd(M[t], T2[t]), cscale(2.0, ct)));
     }
     __syncthreads();
     for (int q = 0; q < P.na; ++q) {  // target part of F_dx_add
         build_target(P, nullptr, b, xb, 1 + q, T1);
-        for (int t = threadIdx.x; t < (int)T; t += blockDim.x) T1[t] = p_scale(P.inv_eps, p_sub(T1[t], U0[t]));
+        for (int t = threadIdx.x; t < (int)T; t += blockDim.x) T1[t] = cscale(P.inv_eps, csub(T1[t], U0[t]));
         __syncthreads();
         bmm<true, false>(T2, T1, U, D);   // Kd
         bmm<false, false>(T1, A, T2, D);  // A Kd
@@ -432,19 +444,19 @@ __global__ __launch_bounds__(SEC_BLOCK) void k_sec_err_head(SectorHead H) {
     bmm<true, false>(T1, Xe, K, D);
     bmm<true, false>(T2, Bm, T1, D);
     for (int t = threadIdx.x; t < (int)T; t += blockDim.x) {
-        M[t] = p_add(p_add(M[t], T2[t]), p_scale(2.0, p_mul(cd{te.re, -te.im}, X[t])));
+        M[t] = cadd(cadd(M[t], T2[t]), cscale(2.0, cmul(cd{te.re, -te.im}, X[t])));
         const int i = t / D, j = t % D;
-        T2[t] = p_add(A[t], p_conj(A[(size_t)j * D + i]));  // A + A^dagger
+        T2[t] = cadd(A[t], cconj(A[(size_t)j * D + i]));  // A + A^dagger
     }
     __syncthreads();
     bmm<true, false>(T1, Ue, U, D);
     bmm<false, false>(T3, T2, T1, D);
     for (int t = threadIdx.x; t < (int)T; t += blockDim.x)
-        M[t] = p_scale(2.0 / P.DD, p_sub(M[t], p_scale(1.0 + P.Dtr, T3[t])));
+        M[t] = cscale(2.0 / P.DD, csub(M[t], cscale(1.0 + P.Dtr, T3[t])));
     __syncthreads();
     for (int q = 0; q < P.na; ++q) {  // target part of F_d2err_dx_add
         build_target(P, nullptr, b, xb, 1 + q, T1);
-        for (int t = threadIdx.x; t < (int)T; t += blockDim.x) T1[t] = p_scale(P.inv_eps, p_sub(T1[t], U0[t]));
+        for (int t = threadIdx.x; t < (int)T; t += blockDim.x) T1[t] = cscale(P.inv_eps, csub(T1[t], U0[t]));
         __syncthreads();
         bmm<true, false>(T2, T1, Ue, D);  // Kde
         bmm<false, false>(T1, A, T2, D);
@@ -467,22 +479,26 @@ __global__ __launch_bounds__(SEC_BLOCK) void k_sec_err_head(SectorHead H) {
     }
 }
 
+
 }  // namespace
 
 
 // ---------------------------------------------------------------------------
 // Diagonal projector and diagonal target (H.diag: the Rydberg CZ problems).  Every matrix of the
 // head is then block-diagonal with the sectors, and k_sec_head's products reduce to sums over
-// the sector blocks of U, one THREAD per evaluation (k_sec_head: one wave per evaluation, ten
-// LDS-staged d x d products; 0.41 ms of a 4.6-ms C2 pass):
+// the sector blocks of U (k_sec_head: one wave per evaluation, ten LDS-staged d x d products;
+// 0.41 ms of a 4.6-ms C2 pass):
 //   K = U0^dag U: K_ij = conj(u0_i) U_ij,   tau = sum_i w_i K_ii,
 //   F = [sum_ij w_i p_j |K_ij|^2 + |tau|^2] / DD                      (FidelityCalculations.jl:54)
 //   M_ij = 2 [p_i (K^dag W K)_ij + conj(tau) w_i K_ij] / DD   (i, j in one sector; k_sec_head's
 //          B (K^dag A K) + B^dag ((A K)^dag K) + 2 conj(tau) A K with A = diag(w), B = diag(p))
 //   target part of F_dx_add (:34-40, 67-76), d = (u0(x_add + eps e_q) - u0) / eps:
 //   [2 sum_ij w_i p_j Re(conj(d_i) U_ij conj(K_ij)) + 2 Re(conj(tau) sum_i w_i conj(d_i) U_ii)] / DD
-// The untouched levels g contribute U_gg = 1.  Sector classes of at most kDiagMaxS levels.
+// The untouched levels g contribute U_gg = 1.  Sector classes of at most kDiagMaxS levels, and at most
+// kDiagMaxRows sector rows in all (the plan sets H.diag only then), so that a group of lanes, one per
+// row, fits a workgroup: both diagonal launchers rest on this bound and have no other path.
 constexpr int kDiagBlock = 64, kDiagMaxS = 4;
+static_assert(kDiagMaxRows <= kDiagBlock, "a diagonal head's row group must fit its workgroup");
 // u[i] = diagonal of the target at x_add (perturbed by pp), i < D, in this thread's LDS row
 __device__ void target_diag(const grape::DevProblem &P, const double *xb, const grape::Pert &pp, cd *u) {
     const double *xadd = xb + (size_t)P.np * P.Nt;
@@ -491,15 +507,15 @@ __device__ void target_diag(const grape::DevProblem &P, const double *xb, const 
         const grape::Term tm = P.tgt[q];
         const cd c = grape::term_coef(tm, 1, xb, xadd, pp);
         const cd *op = P.ops + (size_t)tm.op * P.D * P.D;
-        for (int i = 0; i < P.D; ++i) u[i] = p_add(u[i], p_mul(c, op[(size_t)i * P.D + i]));
+        for (int i = 0; i < P.D; ++i) u[i] = cadd(u[i], cmul(c, op[(size_t)i * P.D + i]));
     }
 }
 __device__ __forceinline__ double pdiag(const grape::DevProblem &P, int g) { return P.W[g] != 0.0 ? 1.0 : 0.0; }
 
 // Row-parallel form (latency).  One thread per evaluation spent 25-30 us on a one-evaluation call:
-// ~3 k dependent FP64 operations and ~100 dependent LDS / global loads in a single lane.  Now a
+// ~3 k dependent FP64 operations and ~100 dependent LDS / global loads in a single lane.  So a
 // GROUP of G lanes serves one evaluation (G = the sector rows sum_c nsec_c S_c rounded up to a
-// power of two: 8 at C2), lane r one row of one sector block; the row sums of F, tau and the
+// power of two: 8 at C2, at most kDiagMaxRows), lane r one row of one sector block; the row sums of F, tau and the
 // F_dx_add terms meet in a shuffle tree (fixed order: deterministic), and each lane writes its
 // row of M_ww.  The workgroup first copies every table it reads and its evaluations' U blocks and
 // x_add values into LDS in one coalesced pass.  Per element the operations are diag_blocks's of
@@ -557,7 +573,7 @@ struct DiagStage {  // the workgroup's LDS copies
 // entry i of the target's diagonal from the term coefficients cq (target_diag's operations)
 __device__ __forceinline__ cd target_entry(const grape::DevProblem &P, const DiagStage &St, const cd *cq, int i) {
     cd u{0.0, 0.0};
-    for (int q = 0; q < P.n_tgt; ++q) u = p_add(u, p_mul(cq[q], St.tdiag[(size_t)q * P.D + i]));
+    for (int q = 0; q < P.n_tgt; ++q) u = cadd(u, cmul(cq[q], St.tdiag[(size_t)q * P.D + i]));
     return u;
 }
 // group sum over G lanes (fixed tree)
@@ -582,7 +598,7 @@ __device__ __forceinline__ void diag_row(const SectorHead &H, const DiagStage &S
     const int gr = St.sidx(cl)[w * S + r];
     // K_kc = conj(u0_{g_k}) U_kc (zero on padding slots)
     auto Kel = [&](int k, int gk, int c, int gc) -> cd {
-        return (gk >= 0 && gc >= 0) ? p_mul(p_conj(u0[gk >= 0 ? gk : 0]), Ub[k * S + c]) : cd{0.0, 0.0};
+        return (gk >= 0 && gc >= 0) ? cmul(cconj(u0[gk >= 0 ? gk : 0]), Ub[k * S + c]) : cd{0.0, 0.0};
     };
     if (pass == 0) {
         if (gr < 0) return;
@@ -593,15 +609,15 @@ __device__ __forceinline__ void diag_row(const SectorHead &H, const DiagStage &S
             const cd K = Kel(r, gr, c, g[c]);
             fsum += wr * pd(g[c]) * (K.re * K.re + K.im * K.im);
         }
-        acc = p_add(acc, p_scale(wr, Kel(r, gr, r, gr)));
+        acc = cadd(acc, cscale(wr, Kel(r, gr, r, gr)));
     } else if (pass == 1 && H.alpha) {
         // the wide pass (one weighted level c per sector): row c of M is alpha U_c. with
         //   alpha = sc W_c conj(u0_c) (p_c conj(K_cc) + conj(tau))
         // (the M row's two terms with U_ce factored out); the weighted row's lane writes it to Msec[b * ns + w]
         if (gr < 0 || St.W[gr] == 0.0) return;
-        const cd kc = p_conj(Kel(r, gr, r, gr));
-        const cd f = p_add(p_scale(pd(gr), kc), cd{tau.re, -tau.im});
-        H.Msec[cl][b * ns + w] = p_scale(sc, p_scale(St.W[gr], p_mul(p_conj(u0[gr]), f)));
+        const cd kc = cconj(Kel(r, gr, r, gr));
+        const cd f = cadd(cscale(pd(gr), kc), cd{tau.re, -tau.im});
+        H.Msec[cl][b * ns + w] = cscale(sc, cscale(St.W[gr], cmul(cconj(u0[gr]), f)));
     } else if (pass == 1) {
         cd *dst = H.Msec[cl] + (b * ns + w) * S * S + (size_t)r * S;
         cd Kr[S];  // column r of K
@@ -614,23 +630,23 @@ __device__ __forceinline__ void diag_row(const SectorHead &H, const DiagStage &S
                 cd s{0.0, 0.0};
 #pragma unroll
                 for (int k = 0; k < S; ++k)
-                    if (g[k] >= 0) s = p_add(s, p_scale(St.W[g[k]], p_mul(p_conj(Kr[k]), Kel(k, g[k], c, g[c]))));
-                m = p_scale(sc, p_add(p_scale(pd(gr), s), p_scale(St.W[gr], p_mul(cd{tau.re, -tau.im}, Kel(r, gr, c, g[c])))));
+                    if (g[k] >= 0) s = cadd(s, cscale(St.W[g[k]], cmul(cconj(Kr[k]), Kel(k, g[k], c, g[c]))));
+                m = cscale(sc, cadd(cscale(pd(gr), s), cscale(St.W[gr], cmul(cd{tau.re, -tau.im}, Kel(r, gr, c, g[c])))));
             }
             dst[c] = m;
         }
     } else {
         if (gr < 0) return;
         const double wr = St.W[gr];
-        const cd dr = p_conj(d[gr]);
+        const cd dr = cconj(d[gr]);
 #pragma unroll
         for (int c = 0; c < S; ++c) {
             if (g[c] < 0) continue;
-            const cd kd = p_mul(dr, Ub[r * S + c]);  // Kd_rc
+            const cd kd = cmul(dr, Ub[r * S + c]);  // Kd_rc
             const cd K = Kel(r, gr, c, g[c]);
             fsum += wr * pd(g[c]) * (kd.re * K.re + kd.im * K.im);
         }
-        acc = p_add(acc, p_scale(wr, p_mul(dr, Ub[r * S + r])));
+        acc = cadd(acc, cscale(wr, cmul(dr, Ub[r * S + r])));
     }
 }
 __device__ __forceinline__ void diag_row_any(const SectorHead &H, const DiagStage &St, int row, int el, size_t b, int pass,
@@ -701,10 +717,7 @@ __global__ __launch_bounds__(kDiagBlock) void k_sec_head_diag(SectorHead H, int 
     cd *u0 = reinterpret_cast<cd *>(diag_smem + Lo.u) + (size_t)el * 2 * P.D, *d = u0 + P.D;
     const double *xb = H.x + b * P.nx;
     const double *xadd = reinterpret_cast<const double *>(diag_smem + Lo.xa) + (size_t)(ok ? el : 0) * P.na;
-    grape::Pert none;
-    none.var = -1;
-    none.index = 0;
-    none.delta = 0.0;
+    const grape::Pert none = no_pert();
     // the target's term coefficients (one lane per term), then its diagonal (one lane per entry)
     cd *cq = reinterpret_cast<cd *>(diag_smem + Lo.cq) + (size_t)el * P.n_tgt;
     if (ok)
@@ -721,25 +734,22 @@ __global__ __launch_bounds__(kDiagBlock) void k_sec_head_diag(SectorHead H, int 
     tau.im = group_add(tau.im, G);
     for (int q = 0; q < H.nfixed; ++q) {  // U_gg = 1: K_gg = conj(u0_g)
         const int g = St.fixed[q];
-        const cd k = p_conj(u0[g]);
+        const cd k = cconj(u0[g]);
         fsum += St.W[g] * (St.W[g] != 0.0 ? 1.0 : 0.0) * (k.re * k.re + k.im * k.im);
-        tau = p_add(tau, p_scale(St.W[g], k));
+        tau = cadd(tau, cscale(St.W[g], k));
     }
     if (ok && row == 0) H.F[b] = (fsum + tau.re * tau.re + tau.im * tau.im) / P.DD;
     double unused = 0.0;
     cd unused_c{0.0, 0.0};
     if (ok) diag_row_any(H, St, row, el, b, 1, u0, d, tau, unused, unused_c);
     for (int q = 0; q < P.na; ++q) {  // target part of F_dx_add
-        grape::Pert pq;
-        pq.var = grape::VAR_XADD;
-        pq.index = q;
-        pq.delta = P.eps;
+        const grape::Pert pq = xadd_pert(P, q);
         __syncthreads();  // every lane is done with the previous d and cq
         if (ok)
             for (int k = row; k < P.n_tgt; k += G) cq[k] = grape::term_coef(St.terms[k], 1, xb, xadd, pq);
         __syncthreads();
         if (ok)
-            for (int i = row; i < P.D; i += G) d[i] = p_scale(P.inv_eps, p_sub(target_entry(P, St, cq, i), u0[i]));
+            for (int i = row; i < P.D; i += G) d[i] = cscale(P.inv_eps, csub(target_entry(P, St, cq, i), u0[i]));
         __syncthreads();
         double sa = 0.0;
         cd trd{0.0, 0.0};
@@ -749,9 +759,9 @@ __global__ __launch_bounds__(kDiagBlock) void k_sec_head_diag(SectorHead H, int 
         trd.im = group_add(trd.im, G);
         for (int r = 0; r < H.nfixed; ++r) {
             const int g = St.fixed[r];
-            const cd kd = p_conj(d[g]), k = p_conj(u0[g]);
+            const cd kd = cconj(d[g]), k = cconj(u0[g]);
             sa += St.W[g] * (St.W[g] != 0.0 ? 1.0 : 0.0) * (kd.re * k.re + kd.im * k.im);
-            trd = p_add(trd, p_scale(St.W[g], kd));
+            trd = cadd(trd, cscale(St.W[g], kd));
         }
         const double val = (2.0 * sa + 2.0 * (tau.re * trd.re + tau.im * trd.im)) / P.DD;
         if (ok && row == 0) {
@@ -761,145 +771,20 @@ __global__ __launch_bounds__(kDiagBlock) void k_sec_head_diag(SectorHead H, int 
     }
 }
 
-// The error head in the same diagonal form, one thread per (evaluation, error source): with
-// Ue = U Tot (block-diagonal, zero on the untouched levels), Ke = U0^dag Ue and K = U0^dag U,
-// k_sec_err_head's products reduce to (A = diag(w), B = diag(p); FidelityCalculations.jl:78-113)
+// The error head in the same diagonal form: with Ue = U Tot (block-diagonal, zero on the untouched
+// levels), Ke = U0^dag Ue and K = U0^dag U, k_sec_err_head's products reduce to (A = diag(w),
+// B = diag(p); FidelityCalculations.jl:78-113)
 //   te = sum_i w_i Ke_ii,  t1 = sum_ij w_i p_j |Ke_ij|^2,  t2 = sum_i w_i (Ue^dag Ue)_ii,
 //   F_d2err = 2 [t1 - (1 + D) t2 + |te|^2] / DD,
 //   M_e,ij = (2/DD) [2 p_i (Ke^dag W K)_ij + 2 conj(te) w_i K_ij - 2 (1 + D) w_i (Ue^dag U)_ij],
 //   target part of F_d2err_dx_add: 2 [2 sum_ij w_i p_j Re(conj(d_i) Ue_ij conj(Ke_ij))
 //                                     + 2 Re(conj(te) sum_i w_i conj(d_i) Ue_ii)] / DD.
-// pass 0: te, t1, t2; pass 1: the blocks of M_e; pass 2: the F_d2err_dx_add sums against d.
-template <int S>
-__device__ void diag_err_blocks(const SectorHead &H, int cl, int b, int e, int pass, const cd *u0, const cd *d, cd te,
-                                double &t1, double &t2, cd &acc) {
-    const grape::DevProblem &P = H.P;
-    const int ns = H.nsec[cl], ne = P.ne;
-    const double sc = 2.0 / P.DD;
-    for (int w = 0; w < ns; ++w) {
-        const size_t bw = (size_t)b * ns + w;
-        const cd *Ub = H.Ub[cl] + bw * S * S, *Tb = H.TotS[cl] + (bw * ne + e) * S * S;
-        int g[S];
-#pragma unroll
-        for (int r = 0; r < S; ++r) g[r] = H.sidx[cl][w * S + r];
-        cd Ue[S][S];
-#pragma unroll
-        for (int r = 0; r < S; ++r) {
-#pragma unroll
-            for (int c = 0; c < S; ++c) {
-                cd v{0.0, 0.0};
-#pragma unroll
-                for (int m = 0; m < S; ++m) v = p_add(v, p_mul(Ub[r * S + m], Tb[m * S + c]));
-                Ue[r][c] = (g[r] >= 0 && g[c] >= 0) ? v : cd{0.0, 0.0};
-            }
-        }
-        auto cu0 = [&](int r) { return p_conj(u0[g[r] >= 0 ? g[r] : 0]); };
-        if (pass == 0) {
-#pragma unroll
-            for (int r = 0; r < S; ++r) {
-                if (g[r] < 0) continue;
-                const double wr = P.W[g[r]];
-                double col = 0.0;  // (Ue^dag Ue)_rr
-#pragma unroll
-                for (int c = 0; c < S; ++c) {
-                    if (g[c] < 0) continue;
-                    const cd ke = p_mul(cu0(r), Ue[r][c]);
-                    t1 += wr * pdiag(P, g[c]) * (ke.re * ke.re + ke.im * ke.im);
-                    col += Ue[c][r].re * Ue[c][r].re + Ue[c][r].im * Ue[c][r].im;
-                }
-                t2 += wr * col;
-                acc = p_add(acc, p_scale(wr, p_mul(cu0(r), Ue[r][r])));
-            }
-        } else if (pass == 1) {
-            cd *dst = H.MsecE[cl] + (bw * ne + e) * S * S;
-#pragma unroll
-            for (int r = 0; r < S; ++r) {
-#pragma unroll
-                for (int c = 0; c < S; ++c) {
-                    cd m{0.0, 0.0};
-                    if (g[r] >= 0 && g[c] >= 0) {
-                        cd kwk{0.0, 0.0}, uu{0.0, 0.0};  // (Ke^dag W K)_rc, (Ue^dag U)_rc
-#pragma unroll
-                        for (int k = 0; k < S; ++k) {
-                            if (g[k] < 0) continue;
-                            const cd kk = p_mul(cu0(k), Ub[k * S + c]), ke = p_mul(cu0(k), Ue[k][r]);
-                            kwk = p_add(kwk, p_scale(P.W[g[k]], p_mul(p_conj(ke), kk)));
-                            uu = p_add(uu, p_mul(p_conj(Ue[k][r]), Ub[k * S + c]));
-                        }
-                        const double wr = P.W[g[r]];
-                        const cd krc = p_mul(cu0(r), Ub[r * S + c]);
-                        m = p_add(p_scale(2.0 * pdiag(P, g[r]), kwk), p_scale(2.0 * wr, p_mul(cd{te.re, -te.im}, krc)));
-                        m = p_scale(sc, p_sub(m, p_scale(2.0 * (1.0 + P.Dtr) * wr, uu)));
-                    }
-                    dst[r * S + c] = m;
-                }
-            }
-        } else {
-#pragma unroll
-            for (int r = 0; r < S; ++r) {
-                if (g[r] < 0) continue;
-                const double wr = P.W[g[r]];
-                const cd dr = p_conj(d[g[r]]);
-#pragma unroll
-                for (int c = 0; c < S; ++c) {
-                    if (g[c] < 0) continue;
-                    const cd kde = p_mul(dr, Ue[r][c]), ke = p_mul(cu0(r), Ue[r][c]);
-                    t1 += wr * pdiag(P, g[c]) * (kde.re * ke.re + kde.im * ke.im);
-                }
-                acc = p_add(acc, p_scale(wr, p_mul(dr, Ue[r][r])));
-            }
-        }
-    }
-}
-__device__ void diag_err_class(const SectorHead &H, int cl, int b, int e, int pass, const cd *u0, const cd *d, cd te,
-                               double &t1, double &t2, cd &acc) {
-    switch (H.S[cl]) {
-    case 2: diag_err_blocks<2>(H, cl, b, e, pass, u0, d, te, t1, t2, acc); break;
-    case 3: diag_err_blocks<3>(H, cl, b, e, pass, u0, d, te, t1, t2, acc); break;
-    default: diag_err_blocks<4>(H, cl, b, e, pass, u0, d, te, t1, t2, acc); break;
-    }
-}
-
-__global__ __launch_bounds__(kDiagBlock) void k_sec_err_head_diag(SectorHead H, int nb) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char diag_smem[];
-    const grape::DevProblem &P = H.P;
-    const int be = blockIdx.x * kDiagBlock + threadIdx.x;
-    if (be >= nb * P.ne) return;
-    const int b = be / P.ne, e = be - b * P.ne;
-    cd *u0 = reinterpret_cast<cd *>(diag_smem) + (size_t)threadIdx.x * 2 * P.D, *d = u0 + P.D;
-    const double *xb = H.x + (size_t)b * P.nx;
-    grape::Pert none;
-    none.var = -1;
-    none.index = 0;
-    none.delta = 0.0;
-    target_diag(P, xb, none, u0);
-    double t1 = 0.0, t2 = 0.0;
-    cd te{0.0, 0.0};
-    for (int cl = 0; cl < H.ncls; ++cl) diag_err_class(H, cl, b, e, 0, u0, d, te, t1, t2, te);
-    H.Fd2[be] = 2.0 * (t1 - (1.0 + P.Dtr) * t2 + te.re * te.re + te.im * te.im) / P.DD;
-    double u1 = 0.0, u2 = 0.0;
-    cd uc{0.0, 0.0};
-    for (int cl = 0; cl < H.ncls; ++cl) diag_err_class(H, cl, b, e, 1, u0, d, te, u1, u2, uc);
-    for (int q = 0; q < P.na; ++q) {  // target part of F_d2err_dx_add
-        grape::Pert pq;
-        pq.var = grape::VAR_XADD;
-        pq.index = q;
-        pq.delta = P.eps;
-        target_diag(P, xb, pq, d);
-        for (int i = 0; i < P.D; ++i) d[i] = p_scale(P.inv_eps, p_sub(d[i], u0[i]));
-        double sa = 0.0, unused = 0.0;
-        cd trd{0.0, 0.0};
-        for (int cl = 0; cl < H.ncls; ++cl) diag_err_class(H, cl, b, e, 2, u0, d, te, sa, unused, trd);
-        H.Fd2dx[(size_t)be * P.nx + (size_t)P.np * P.Nt + q] = 2.0 * (2.0 * sa + 2.0 * (te.re * trd.re + te.im * trd.im)) / P.DD;
-    }
-}
-
-// Row-parallel form of k_sec_err_head_diag (round 6, latency): one group of G lanes per (evaluation, error
-// source), lane = row r of one sector block, as k_sec_head_diag.  Pass 0 forms row r of Ue = U Tot and its
-// terms of te, t1, t2 (t2 regrouped by rows: sum_rc w_c |Ue_rc|^2), a shuffle tree sums them; row r of Ue
-// goes to LDS, and pass 1 writes row r of M_e from the block's columns; pass 2 the F_d2err_dx_add row terms.
-// Lane 0 of the group forms the target's diagonal (target_diag).  The per-element operations are
-// diag_err_blocks's; only the order of the sums over rows changed.  One C3 evaluation: 36.9 us in one lane.
+// Row-parallel as k_sec_head_diag: one group of G lanes per (evaluation, error source), lane = row r of
+// one sector block.  Pass 0 forms row r of Ue and its terms of te, t1, t2 (t2 regrouped by rows:
+// sum_rc w_c |Ue_rc|^2), a shuffle tree sums them; row r of Ue goes to LDS, and pass 1 writes row r of
+// M_e from the block's columns; pass 2 the F_d2err_dx_add row terms against d.  Lane 0 of the group
+// forms the target's diagonal (target_diag).  (Its predecessor ran one lane per (evaluation, error
+// source) over whole blocks, 36.9 us for one C3 evaluation; only the order of the sums over rows changed.)
 template <int S>
 __device__ void err_row(const SectorHead &H, int cl, int w, int r, size_t b, int e, int pass, const cd *u0, const cd *d,
                         cd te, cd *ue, double &t1, double &t2, cd &acc) {
@@ -912,7 +797,7 @@ __device__ void err_row(const SectorHead &H, int cl, int w, int r, size_t b, int
 #pragma unroll
     for (int k = 0; k < S; ++k) g[k] = H.sidx[cl][w * S + k];
     const int gr = g[r];
-    auto cu0 = [&](int k) { return p_conj(u0[g[k] >= 0 ? g[k] : 0]); };
+    auto cu0 = [&](int k) { return cconj(u0[g[k] >= 0 ? g[k] : 0]); };
     if (pass == 0) {
         const cd *Tb = H.TotS[cl] + (bw * ne + e) * S * S;
         cd Ur[S];
@@ -920,7 +805,7 @@ __device__ void err_row(const SectorHead &H, int cl, int w, int r, size_t b, int
         for (int c = 0; c < S; ++c) {
             cd v{0.0, 0.0};
 #pragma unroll
-            for (int m = 0; m < S; ++m) v = p_add(v, p_mul(Ub[r * S + m], Tb[m * S + c]));
+            for (int m = 0; m < S; ++m) v = cadd(v, cmul(Ub[r * S + m], Tb[m * S + c]));
             Ur[c] = (gr >= 0 && g[c] >= 0) ? v : cd{0.0, 0.0};
             ue[r * S + c] = Ur[c];
         }
@@ -929,11 +814,11 @@ __device__ void err_row(const SectorHead &H, int cl, int w, int r, size_t b, int
 #pragma unroll
         for (int c = 0; c < S; ++c) {
             if (g[c] < 0) continue;
-            const cd ke = p_mul(cu0(r), Ur[c]);
+            const cd ke = cmul(cu0(r), Ur[c]);
             t1 += wr * pdiag(P, g[c]) * (ke.re * ke.re + ke.im * ke.im);
             t2 += P.W[g[c]] * (Ur[c].re * Ur[c].re + Ur[c].im * Ur[c].im);
         }
-        acc = p_add(acc, p_scale(wr, p_mul(cu0(r), Ur[r])));
+        acc = cadd(acc, cscale(wr, cmul(cu0(r), Ur[r])));
     } else if (pass == 1) {
         cd *dst = H.MsecE[cl] + (bw * ne + e) * S * S + (size_t)r * S;
 #pragma unroll
@@ -944,28 +829,28 @@ __device__ void err_row(const SectorHead &H, int cl, int w, int r, size_t b, int
 #pragma unroll
                 for (int k = 0; k < S; ++k) {
                     if (g[k] < 0) continue;
-                    const cd kk = p_mul(cu0(k), Ub[k * S + c]), ke = p_mul(cu0(k), ue[k * S + r]);
-                    kwk = p_add(kwk, p_scale(P.W[g[k]], p_mul(p_conj(ke), kk)));
-                    uu = p_add(uu, p_mul(p_conj(ue[k * S + r]), Ub[k * S + c]));
+                    const cd kk = cmul(cu0(k), Ub[k * S + c]), ke = cmul(cu0(k), ue[k * S + r]);
+                    kwk = cadd(kwk, cscale(P.W[g[k]], cmul(cconj(ke), kk)));
+                    uu = cadd(uu, cmul(cconj(ue[k * S + r]), Ub[k * S + c]));
                 }
                 const double wr = P.W[gr];
-                const cd krc = p_mul(cu0(r), Ub[r * S + c]);
-                m = p_add(p_scale(2.0 * pdiag(P, gr), kwk), p_scale(2.0 * wr, p_mul(cd{te.re, -te.im}, krc)));
-                m = p_scale(sc, p_sub(m, p_scale(2.0 * (1.0 + P.Dtr) * wr, uu)));
+                const cd krc = cmul(cu0(r), Ub[r * S + c]);
+                m = cadd(cscale(2.0 * pdiag(P, gr), kwk), cscale(2.0 * wr, cmul(cd{te.re, -te.im}, krc)));
+                m = cscale(sc, csub(m, cscale(2.0 * (1.0 + P.Dtr) * wr, uu)));
             }
             dst[c] = m;
         }
     } else {
         if (gr < 0) return;
         const double wr = P.W[gr];
-        const cd dr = p_conj(d[gr]);
+        const cd dr = cconj(d[gr]);
 #pragma unroll
         for (int c = 0; c < S; ++c) {
             if (g[c] < 0) continue;
-            const cd kde = p_mul(dr, ue[r * S + c]), ke = p_mul(cu0(r), ue[r * S + c]);
+            const cd kde = cmul(dr, ue[r * S + c]), ke = cmul(cu0(r), ue[r * S + c]);
             t1 += wr * pdiag(P, g[c]) * (kde.re * ke.re + kde.im * ke.im);
         }
-        acc = p_add(acc, p_scale(wr, p_mul(dr, ue[r * S + r])));
+        acc = cadd(acc, cscale(wr, cmul(dr, ue[r * S + r])));
     }
 }
 __device__ __forceinline__ void err_row_any(const SectorHead &H, int row, size_t b, int e, int pass, const cd *u0,
@@ -1001,10 +886,7 @@ __global__ __launch_bounds__(kDiagBlock) void k_sec_err_head_rows(SectorHead H, 
     const int bb = ok ? be : 0, b = bb / P.ne, e = bb - b * P.ne;
     cd *u0 = reinterpret_cast<cd *>(diag_smem) + (size_t)el * err_rows_group_cd(H), *d = u0 + P.D, *ue = d + P.D;
     const double *xb = H.x + (size_t)b * P.nx;
-    grape::Pert none;
-    none.var = -1;
-    none.index = 0;
-    none.delta = 0.0;
+    const grape::Pert none = no_pert();
     if (ok && row == 0) target_diag(P, xb, none, u0);
     __syncthreads();
     double t1 = 0.0, t2 = 0.0;
@@ -1020,14 +902,11 @@ __global__ __launch_bounds__(kDiagBlock) void k_sec_err_head_rows(SectorHead H, 
     cd uc{0.0, 0.0};
     if (ok) err_row_any(H, row, b, e, 1, u0, d, te, ue, u1, u2, uc);
     for (int q = 0; q < P.na; ++q) {  // target part of F_d2err_dx_add
-        grape::Pert pq;
-        pq.var = grape::VAR_XADD;
-        pq.index = q;
-        pq.delta = P.eps;
+        const grape::Pert pq = xadd_pert(P, q);
         __syncthreads();
         if (ok && row == 0) {
             target_diag(P, xb, pq, d);
-            for (int i = 0; i < P.D; ++i) d[i] = p_scale(P.inv_eps, p_sub(d[i], u0[i]));
+            for (int i = 0; i < P.D; ++i) d[i] = cscale(P.inv_eps, csub(d[i], u0[i]));
         }
         __syncthreads();
         double sa = 0.0, unused = 0.0;
@@ -1043,17 +922,10 @@ __global__ __launch_bounds__(kDiagBlock) void k_sec_err_head_rows(SectorHead H, 
 
 hipError_t launch_sector_err_head(const SectorHead &H, int nb, hipStream_t st) {
     if (H.P.ne == 0) return hipSuccess;
-    if (H.diag && diag_group(H) <= kDiagBlock) {
+    if (H.diag) {  // G <= kDiagMaxRows lanes per (evaluation, error source)
         const int G = diag_group(H), EB = kDiagBlock / G, n = nb * H.P.ne;
         const size_t lds = (size_t)EB * err_rows_group_cd(H) * sizeof(cd);
         hipLaunchKernelGGL(k_sec_err_head_rows, dim3((unsigned)((n + EB - 1) / EB)), dim3(kDiagBlock), lds, st, H, nb);
-        return hipGetLastError();
-    }
-    if (H.diag) {
-        const int n = nb * H.P.ne;
-        const size_t lds = (size_t)kDiagBlock * 2 * H.P.D * sizeof(cd);
-        hipLaunchKernelGGL(k_sec_err_head_diag, dim3((unsigned)((n + kDiagBlock - 1) / kDiagBlock)), dim3(kDiagBlock),
-                           lds, st, H, nb);
         return hipGetLastError();
     }
     const size_t lds = (size_t)kErrHeadSlots * H.P.D * H.P.D * sizeof(cd);
@@ -1063,7 +935,7 @@ hipError_t launch_sector_err_head(const SectorHead &H, int nb, hipStream_t st) {
 
 hipError_t launch_sector_head(const SectorHead &H, int nb, hipStream_t st) {
     if (H.diag) {
-        const DiagLayout L = diag_layout(H);  // G lanes per evaluation (G <= 16: d <= 12, sectors of <= 4 levels)
+        const DiagLayout L = diag_layout(H);  // G <= kDiagMaxRows lanes per evaluation
         hipLaunchKernelGGL(k_sec_head_diag, dim3((unsigned)((nb + L.EB - 1) / L.EB)), dim3(kDiagBlock), L.total, st, H,
                            nb);
         return hipGetLastError();

@@ -40,6 +40,7 @@ hipError_t launch_err_head(const Heads &H, int nb, hipStream_t st);
 // exactly as k_proj_fid does (with A = P0 P, B = P, any projector), and stores the sector
 // blocks M_ww; k_sec_mc then forms the per-chunk images M'_{c,w} = Carry M_ww Carry^dagger
 // that the sector k_expm_grad contracts.
+constexpr int kDiagMaxRows = 32;  // SectorHead::diag: at most this many sector rows, sum_c nsec[c] * S[c]
 struct SectorHead {
     grape::DevProblem P;      // the FULL d-dimensional problem (target terms, operators, PA / PB), d <= 12
     int ncls;                 // sector classes (1 or 2), each of nsec[c] sectors of S[c] slots
@@ -56,15 +57,17 @@ struct SectorHead {
     const grape::cd *TotS[2]; // [nb * nsec][ne][S][S]
     grape::cd *MsecE[2];      // [nb * nsec][ne][S][S]  (written)
     double *Fd2, *Fd2dx;
-    int diag;                 // diagonal projector and target, sector classes of <= 4 levels: the
-                              // fidelity head runs one thread per evaluation on the sector blocks
+    int diag;                 // diagonal projector and target, sector classes of <= 4 levels, <= kDiagMaxRows
+                              // sector rows: both heads run on the sector blocks, one lane per row, a group
+                              // of lanes per evaluation (and error source); the only path of a diag head
     int alpha;                // diag, the wide pass (grape_walk_api.hpp launch_merged_wide): every sector has one
                               // weighted level c and Ub holds column c only; instead of the M blocks the head
                               // writes alpha per sector, Msec[c] = [nb * nsec], where row c of M is alpha U_c.
 };
 // (kSectorLds, the LDS capacity for the sector blocks M_ww: grape_types.hpp)
 hipError_t launch_sector_head(const SectorHead &H, int nb, hipStream_t st);
-// one wave per (evaluation, error source): F_d2err, M_e blocks, F_d2err_dx_add target part
+// F_d2err, M_e blocks, F_d2err_dx_add target part: one wave per (evaluation, error source), or (diag) one
+// group of lanes
 hipError_t launch_sector_err_head(const SectorHead &H, int nb, hipStream_t st);
 
 // the small engine's view (grape_launch.hpp)

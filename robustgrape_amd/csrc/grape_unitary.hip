@@ -35,10 +35,7 @@ namespace {
 
 constexpr int BLOCK = 256;  // >= d^2 for d <= 12 (kMaxD)
 
-__device__ __forceinline__ cd u_add(cd a, cd b) { return cd{a.re + b.re, a.im + b.im}; }
-__device__ __forceinline__ cd u_sub(cd a, cd b) { return cd{a.re - b.re, a.im - b.im}; }
-__device__ __forceinline__ cd u_scale(double s, cd a) { return cd{s * a.re, s * a.im}; }
-__device__ __forceinline__ cd u_mul(cd a, cd b) { return cd{a.re * b.re - a.im * b.im, a.re * b.im + a.im * b.re}; }
+using grape::cadd, grape::csub, grape::cscale, grape::cmul;  // grape_device.hpp: plain, unfused
 __device__ __forceinline__ cd u_mulc(cd a, cd b) {  // conj(a) b
     return cd{a.re * b.re + a.im * b.im, a.re * b.im - a.im * b.re};
 }
@@ -46,13 +43,13 @@ __device__ __forceinline__ cd u_mulc(cd a, cd b) {  // conj(a) b
 // element (i, j) of A B, A and B row-major D x D
 __device__ __forceinline__ cd mm_el(const cd *A, const cd *B, int D, int i, int j) {
     cd s{0.0, 0.0};
-    for (int l = 0; l < D; ++l) s = u_add(s, u_mul(A[i * D + l], B[l * D + j]));
+    for (int l = 0; l < D; ++l) s = cadd(s, cmul(A[i * D + l], B[l * D + j]));
     return s;
 }
 // element (i, j) of A^dagger B
 __device__ __forceinline__ cd mmh_el(const cd *A, const cd *B, int D, int i, int j) {
     cd s{0.0, 0.0};
-    for (int l = 0; l < D; ++l) s = u_add(s, u_mulc(A[l * D + i], B[l * D + j]));
+    for (int l = 0; l < D; ++l) s = cadd(s, u_mulc(A[l * D + i], B[l * D + j]));
     return s;
 }
 
@@ -146,14 +143,14 @@ __global__ __launch_bounds__(BLOCK) void k_u_inverse(UProblem P, const cd *C, cd
             for (int t = t0; t < 2 * D; t += blockDim.x) {  // pivot row * (1 / pivot)
                 cd *M = t < D ? sA : sI;
                 const int j = t < D ? t : t - D;
-                M[c * D + j] = u_mul(M[c * D + j], rp);
+                M[c * D + j] = cmul(M[c * D + j], rp);
             }
             for (int i = t0; i < D; i += blockDim.x) fac[i] = i == c ? cd{0.0, 0.0} : sA[i * D + c];
             tsync();
             for (int t = t0; t < 2 * DD; t += blockDim.x) {  // eliminate column c from every other row
                 cd *M = t < DD ? sA : sI;
                 const int e = t < DD ? t : t - DD, i = e / D, j = e % D;
-                if (i != c) M[e] = u_sub(M[e], u_mul(fac[i], M[c * D + j]));
+                if (i != c) M[e] = csub(M[e], cmul(fac[i], M[c * D + j]));
             }
             tsync();
         }
@@ -172,17 +169,17 @@ __device__ __forceinline__ cd stencil(const UProblem &P, const cd *Ek, int s, in
     const int DD = P.D * P.D;
     const cd e0 = Ek[t];
     if (s < P.np + P.na)  // dx_p / dxa_q: inv_eps * (E' - E)
-        return u_scale(P.inv_eps, u_sub(Ek[(size_t)(1 + s) * DD + t], e0));
+        return cscale(P.inv_eps, csub(Ek[(size_t)(1 + s) * DD + t], e0));
     s -= P.np + P.na;
     if (s < P.ne)  // err_e
-        return u_scale(P.inv_eps, u_sub(Ek[(size_t)P.v_err(s) * DD + t], e0));
+        return cscale(P.inv_eps, csub(Ek[(size_t)P.v_err(s) * DD + t], e0));
     s -= P.ne;
     // mixed: (E(x + eps2, err eps2) + E - E(err eps2) - E(x + eps2)) / eps2^2
     const int nq = P.np + P.na, e = s / nq, q = s % nq;
     const cd a = Ek[(size_t)P.v_mix(e, q) * DD + t];
     const cd b = Ek[(size_t)P.v_err2(e) * DD + t];
     const cd c = Ek[(size_t)P.v_x2(q) * DD + t];
-    return u_scale(P.inv_eps2sq, u_sub(u_sub(u_add(a, e0), b), c));
+    return cscale(P.inv_eps2sq, csub(csub(cadd(a, e0), b), c));
 }
 
 // V_{k,s} = C_k^-1 stencil C_{k-1}, items (k, s); C_k^-1 = C_k^dagger unless Ci is given
@@ -215,7 +212,7 @@ __global__ void k_u_cumsum(UProblem P, const cd *V, cd *S) {
     const int s = P.np + P.na + e;
     cd acc{0.0, 0.0};
     for (int k = 0; k < P.Nt; ++k) {
-        acc = u_add(acc, V[((size_t)k * P.nslots + s) * DD + t]);
+        acc = cadd(acc, V[((size_t)k * P.nslots + s) * DD + t]);
         S[((size_t)k * P.ne + e) * DD + t] = acc;
     }
 }
@@ -248,14 +245,14 @@ __global__ __launch_bounds__(BLOCK) void k_u_assemble(UProblem P, const cd *C, c
         tsync();
         if (k < P.Nt - 1) {  // R_{k+1,e} = S_{N-1,e} - S_{k,e}
             const cd *Stot = S + ((size_t)(P.Nt - 1) * P.ne + e) * DD, *Sk = S + ((size_t)k * P.ne + e) * DD;
-            for (int q = t0; q < DD; q += blockDim.x) sB[q] = u_sub(Stot[q], Sk[q]);
+            for (int q = t0; q < DD; q += blockDim.x) sB[q] = csub(Stot[q], Sk[q]);
         }
         tsync();
         const int smix = P.np + P.na + P.ne + e * (P.np + P.na) + p;
         for (int t = t0; t < DD; t += blockDim.x) {
             cd x = sX[t];
-            if (k < P.Nt - 1) x = u_add(x, mm_el(sB, sA, D, t / D, t % D));
-            sX[t] = u_add(x, V[((size_t)k * P.nslots + smix) * DD + t]);
+            if (k < P.Nt - 1) x = cadd(x, mm_el(sB, sA, D, t / D, t % D));
+            sX[t] = cadd(x, V[((size_t)k * P.nslots + smix) * DD + t]);
         }
         tsync();
         for (int t = t0; t < DD; t += blockDim.x)
@@ -281,7 +278,7 @@ __global__ __launch_bounds__(BLOCK) void k_u_reduce(UProblem P, const cd *C, con
             const int s = P.np + m;
             for (int t = t0; t < DD; t += blockDim.x) {
                 cd acc{0.0, 0.0};
-                for (int k = 0; k < P.Nt; ++k) acc = u_add(acc, V[((size_t)k * P.nslots + s) * DD + t]);
+                for (int k = 0; k < P.Nt; ++k) acc = cadd(acc, V[((size_t)k * P.nslots + s) * DD + t]);
                 sX[t] = acc;
             }
             out = Udxa;
@@ -301,19 +298,19 @@ __global__ __launch_bounds__(BLOCK) void k_u_reduce(UProblem P, const cd *C, con
                 if (k > 0) load_tile(sB, S + ((size_t)(k - 1) * P.ne + e) * DD, D);
                 tsync();
                 if (k > 0)
-                    for (int t = t0; t < DD; t += blockDim.x) sX[t] = u_add(sX[t], mm_el(sA, sB, D, t / D, t % D));
+                    for (int t = t0; t < DD; t += blockDim.x) sX[t] = cadd(sX[t], mm_el(sA, sB, D, t / D, t % D));
                 tsync();
                 if (k < P.Nt - 1) {
                     const cd *Sk = S + ((size_t)k * P.ne + e) * DD;
-                    for (int w = t0; w < DD; w += blockDim.x) sB[w] = u_sub(Stot[w], Sk[w]);
+                    for (int w = t0; w < DD; w += blockDim.x) sB[w] = csub(Stot[w], Sk[w]);
                 }
                 tsync();
                 if (k < P.Nt - 1)
-                    for (int t = t0; t < DD; t += blockDim.x) sX[t] = u_add(sX[t], mm_el(sB, sA, D, t / D, t % D));
+                    for (int t = t0; t < DD; t += blockDim.x) sX[t] = cadd(sX[t], mm_el(sB, sA, D, t / D, t % D));
             }
             for (int t = t0; t < DD; t += blockDim.x) {
                 cd acc = sX[t];
-                for (int k = 0; k < P.Nt; ++k) acc = u_add(acc, V[((size_t)k * P.nslots + smix) * DD + t]);
+                for (int k = 0; k < P.Nt; ++k) acc = cadd(acc, V[((size_t)k * P.nslots + smix) * DD + t]);
                 sX[t] = acc;
             }
             out = Uedxa;
@@ -352,12 +349,12 @@ __global__ __launch_bounds__(BLOCK) void k_u_interaction(grape::DevProblem P, co
                 if (fac) {  // product coefficients: the term's factor slots (real values; op = 0: empty)
                     for (int j = 0; j < grape::kMaxFactors; ++j) {
                         const grape::Term f = fac[(size_t)q * grape::kMaxFactors + j];
-                        if (f.op) c = u_scale(grape::term_coef(f, k + 1, xk, xadd, none).re, c);
+                        if (f.op) c = cscale(grape::term_coef(f, k + 1, xk, xadd, none).re, c);
                     }
                 }
-                h = u_add(h, u_mul(c, P.ops[(size_t)tm.op * DD + t]));
+                h = cadd(h, cmul(c, P.ops[(size_t)tm.op * DD + t]));
             }
-            sH[t] = u_scale(1.0 / P.eps, u_scale(P.eps, h));
+            sH[t] = cscale(1.0 / P.eps, cscale(P.eps, h));
         }
         tsync();
         for (int t = t0; t < DD; t += blockDim.x) sT[t] = mm_el(sH, sC, D, t / D, t % D);
@@ -402,9 +399,9 @@ __global__ void k_u_expect(grape::DevProblem P, const cd *O, double *ev) {
         if (P.gen_proj) {  // tr(P0 O) = sum_ij P0_ij O_ji for a general projector
             for (int i = 0; i < D; ++i)
                 for (int j = 0; j < D; ++j)
-                    acc = u_add(acc, u_mul(P.P0g[i * D + j], O[cm(D, (size_t)e * P.Nt + k, j, i)]));
+                    acc = cadd(acc, cmul(P.P0g[i * D + j], O[cm(D, (size_t)e * P.Nt + k, j, i)]));
         } else {
-            for (int i = 0; i < D; ++i) acc = u_add(acc, u_scale(P.W[i], O[cm(D, (size_t)e * P.Nt + k, i, i)]));
+            for (int i = 0; i < D; ++i) acc = cadd(acc, cscale(P.W[i], O[cm(D, (size_t)e * P.Nt + k, i, i)]));
         }
         ev[(size_t)e * P.Nt + k] = P.dt * acc.re / P.Dtr;
     }
@@ -439,7 +436,7 @@ __device__ void mm(cd *C, const cd *A, int ha, const cd *B, int hb, int D) {
         for (int l = 0; l < D; ++l) {
             const cd a = ha ? cd{A[l * D + i].re, -A[l * D + i].im} : A[i * D + l];
             const cd b = hb ? cd{B[j * D + l].re, -B[j * D + l].im} : B[l * D + j];
-            s = u_add(s, u_mul(a, b));
+            s = cadd(s, cmul(a, b));
         }
         C[t] = s;
     }
@@ -451,7 +448,7 @@ __device__ cd bsum(cd v, cd *red) {
     red[threadIdx.x] = v;
     tsync();
     for (int w = blockDim.x / 2; w > 0; w >>= 1) {
-        if ((int)threadIdx.x < w) red[threadIdx.x] = u_add(red[threadIdx.x], red[threadIdx.x + w]);
+        if ((int)threadIdx.x < w) red[threadIdx.x] = cadd(red[threadIdx.x], red[threadIdx.x + w]);
         tsync();
     }
     const cd r = red[0];
@@ -461,13 +458,13 @@ __device__ cd bsum(cd v, cd *red) {
 // tr(A B) = sum_ij A_ij B_ji
 __device__ cd trace_ab(const cd *A, const cd *B, int D, cd *red) {
     cd s{0.0, 0.0};
-    for (int t = threadIdx.x; t < D * D; t += blockDim.x) s = u_add(s, u_mul(A[t], B[(t % D) * D + t / D]));
+    for (int t = threadIdx.x; t < D * D; t += blockDim.x) s = cadd(s, cmul(A[t], B[(t % D) * D + t / D]));
     return bsum(s, red);
 }
 // sum_ij A_ij conj(B_ij) = tr(A B^dagger)
 __device__ cd trace_abh(const cd *A, const cd *B, int D, cd *red) {
     cd s{0.0, 0.0};
-    for (int t = threadIdx.x; t < D * D; t += blockDim.x) s = u_add(s, u_mul(A[t], cd{B[t].re, -B[t].im}));
+    for (int t = threadIdx.x; t < D * D; t += blockDim.x) s = cadd(s, cmul(A[t], cd{B[t].re, -B[t].im}));
     return bsum(s, red);
 }
 // column-major global matrix -> row-major LDS tile
@@ -492,7 +489,7 @@ __device__ void target(cd *dst, const FidArgs &A, int slot) {
         cd h{0.0, 0.0};
         for (int q = 0; q < P.n_tgt; ++q) {
             const grape::Term tm = P.tgt[q];
-            h = u_add(h, u_mul(grape::term_coef(tm, 1, A.x, xadd, pp), P.ops[(size_t)tm.op * DD + t]));
+            h = cadd(h, cmul(grape::term_coef(tm, 1, A.x, xadd, pp), P.ops[(size_t)tm.op * DD + t]));
         }
         dst[t] = h;
     }
@@ -531,15 +528,15 @@ __global__ __launch_bounds__(BLOCK) void k_u_fid_head(FidArgs A) {
     fid::mm(T1, K, 1, PA, 1, D);
     fid::mm(T3, PB, 1, T1, 0, D);
     for (int t = threadIdx.x; t < DD; t += blockDim.x)
-        T1[t] = u_add(u_add(T2[t], T3[t]), u_mul(cd{2.0 * tau.re, -2.0 * tau.im}, PA[t]));
+        T1[t] = cadd(cadd(T2[t], T3[t]), cmul(cd{2.0 * tau.re, -2.0 * tau.im}, PA[t]));
     tsync();
     fid::mm(T2, T1, 0, U0, 1, D);
-    for (int t = threadIdx.x; t < DD; t += blockDim.x) A.G[t] = u_scale(1.0 / Dn, T2[t]);
+    for (int t = threadIdx.x; t < DD; t += blockDim.x) A.G[t] = cscale(1.0 / Dn, T2[t]);
     tsync();
     // x_add: F_dx_add[q] = Re tr(U_dx_add[q] G) + target-derivative terms (:66-76)
     for (int q = 0; q < na; ++q) {
         fid::target(U0d, A, 1 + q);
-        for (int t = threadIdx.x; t < DD; t += blockDim.x) U0d[t] = u_scale(P.inv_eps, u_sub(U0d[t], U0[t]));
+        for (int t = threadIdx.x; t < DD; t += blockDim.x) U0d[t] = cscale(P.inv_eps, csub(U0d[t], U0[t]));
         tsync();
         fid::mm(Kd, U0d, 1, U, 0, D);  // Kd = U0d^dag U
         fid::mm(T1, Kd, 0, PB, 0, D);
@@ -569,25 +566,25 @@ __global__ __launch_bounds__(BLOCK) void k_u_fid_head(FidArgs A) {
         fid::mm(T1, Ke, 1, PA, 1, D);
         fid::mm(T3, PB, 1, T1, 0, D);
         for (int t = threadIdx.x; t < DD; t += blockDim.x)
-            T1[t] = u_add(u_add(T2[t], T3[t]), u_mul(cd{2.0 * sg.re, -2.0 * sg.im}, PA[t]));
+            T1[t] = cadd(cadd(T2[t], T3[t]), cmul(cd{2.0 * sg.re, -2.0 * sg.im}, PA[t]));
         tsync();
         fid::mm(T2, T1, 0, U0, 1, D);
         for (int t = threadIdx.x; t < DD; t += blockDim.x) {  // (PA^dag + PA)
             const int i = t / D, j = t % D;
-            T1[t] = u_add(cd{PA[j * D + i].re, -PA[j * D + i].im}, PA[t]);
+            T1[t] = cadd(cd{PA[j * D + i].re, -PA[j * D + i].im}, PA[t]);
         }
         tsync();
         fid::mm(T3, T1, 0, Ue, 1, D);
         cd *Ge = A.G + (size_t)(1 + e) * DD;
         for (int t = threadIdx.x; t < DD; t += blockDim.x) {
-            T2[t] = u_scale(2.0 / Dn, u_sub(T2[t], u_scale(1.0 + Dtr, T3[t])));  // kept for the x_add entries
+            T2[t] = cscale(2.0 / Dn, csub(T2[t], cscale(1.0 + Dtr, T3[t])));  // kept for the x_add entries
             Ge[t] = T2[t];
         }
         tsync();
         // F_d2err_dx_add[q, e] = Re tr(U_derr_dx_add[q, e] G_e) + target-derivative terms (:99-113)
         for (int q = 0; q < na; ++q) {
             fid::target(U0d, A, 1 + q);
-            for (int t = threadIdx.x; t < DD; t += blockDim.x) U0d[t] = u_scale(P.inv_eps, u_sub(U0d[t], U0[t]));
+            for (int t = threadIdx.x; t < DD; t += blockDim.x) U0d[t] = cscale(P.inv_eps, csub(U0d[t], U0[t]));
             tsync();
             fid::mm(Kd, U0d, 1, Ue, 0, D);  // Ked = U0d^dag Ue
             fid::mm(T1, Kd, 0, PB, 0, D);

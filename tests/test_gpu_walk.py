@@ -272,9 +272,9 @@ def test_walk_propagator_modes_bitwise(name, fp):
                                      ("sym5-amp-freq", lambda: P.sym_problem(30, errors=("amp", "freq"))),
                                      ("fullblk7-amp", lambda: P.fullblk_problem(30, errors=("amp",)))])
 def test_diagonal_head_matches_general_head(name, fp):
-    """Diagonal projector and target (every Rydberg CZ problem): the one-thread-per-evaluation sector
-    heads (grape_projector.hip k_sec_head_diag, k_sec_err_head_diag) against the general d x d heads
-    (GRAPE_OPT_GENERAL_HEAD)
+    """Diagonal projector and target (every Rydberg CZ problem): the row-parallel sector heads
+    (grape_projector.hip k_sec_head_diag, k_sec_err_head_rows: one lane per row of a sector block)
+    against the general d x d heads (GRAPE_OPT_GENERAL_HEAD: k_sec_head, k_sec_err_head)
     -- F, the target part of F_dx_add and, through M, every F_dx / F_d2err / F_d2err_dx entry, at the
     rounding level of the two summation orders."""
     from robustgrape_amd.operators import OPT_GENERAL_HEAD
