@@ -130,9 +130,10 @@ static KMark profiling_mark(grape_plan *p) {  // per-kernel event pairs on the s
 }
 
 // One wide pass (grape_walk_api.hpp launch_merged_wide) of nb == p->wide evaluations on the caller's buffers:
-// the forward state walk, the head (alpha per sector instead of the M blocks), the time-reversed gradient walk.
-// The U blocks and the alphas live in the chunk totals' and the carries' buffers, which hold exactly
+// the forward state walk, the head (k_wide_head: alpha per sector instead of the M blocks), the time-reversed
+// gradient walk.  psi_N and the alphas live in the chunk totals' and the carries' buffers, which hold exactly
 // max_batch x nchunks tiles per sector and are idle here (no chunks); later chunked passes follow in stream order.
+// psi_N is evaluation-minor, entry j of chain ch of a class at [(ch * D + j) * nb + b] (twin sectors share chain 0).
 static int enqueue_wide(grape_plan *p, int nb, const double *d_x, double *d_F, double *d_Fdx) {
     hipStream_t st = p->stream;
     p->cur_stream = st;
@@ -140,7 +141,6 @@ static int enqueue_wide(grape_plan *p, int nb, const double *d_x, double *d_F, d
     const int ma = p->merge_pa, mb = 1 - ma;
     DevProblem Pw[2] = {p->Ps[ma], p->Ps[mb]};
     DevBatch Bw[2]{};
-    grape_proj::SectorHead H = p->SH;
     for (int i = 0; i < 2; ++i) {
         const int cl = i == 0 ? ma : mb;
         const grape_plan::SecBuf &sb = p->sb[cl];
@@ -154,19 +154,32 @@ static int enqueue_wide(grape_plan *p, int nb, const double *d_x, double *d_F, d
         Bw[i].Msec = sb.Carry;
         Bw[i].status = p->d_ctrl + 2;
         Bw[i].sink = p->d_sink;
-        H.Ub[cl] = sb.Tc;
-        H.Msec[cl] = sb.Carry;
     }
-    H.alpha = 1;
+    grape_proj::WideHead H{};
+    H.P = p->SH.P;
+    H.fixed = p->SH.fixed;
+    H.nfixed = p->SH.nfixed;
     H.x = d_x;
     H.F = d_F;
     H.Fdx = d_Fdx;
-    H.tgt_part = p->d_tgt_part;
+    int ns = 0;
+    for (int cl = 0; cl < 2; ++cl) {  // the sectors in the head's class order
+        const DevProblem &Pc = p->Ps[cl];
+        for (int w = 0; w < Pc.nsec; ++w, ++ns) {
+            if (ns == 3) return fail(GRAPE_ERR_HIP, "wide pass: more than three sectors");
+            const int ch = (cl == mb && Pc.twin) ? 0 : w;
+            H.lev[ns] = p->wide_lev[cl][w];
+            H.ucc[ns] = p->sb[cl].Tc + ((size_t)ch * Pc.D + Pc.rank1_c[w]) * nb;
+            H.alpha[ns] = p->sb[cl].Carry + w;
+            H.astride[ns] = Pc.nsec;
+        }
+    }
+    if (ns != 3) return fail(GRAPE_ERR_HIP, "wide pass: fewer than three sectors");
     mk(GRAPE_KERNEL_WALK_FWD, 0);
     HIPCHECK(grape_walk::launch_merged_wide(0, Pw[0], Bw[0], Pw[1], Bw[1], st));
     mk(GRAPE_KERNEL_WALK_FWD, 1);
     mk(GRAPE_KERNEL_SCAN, 0);
-    HIPCHECK(grape_proj::launch_sector_head(H, nb, st));
+    HIPCHECK(grape_proj::launch_wide_head(H, nb, st));
     mk(GRAPE_KERNEL_SCAN, 1);
     mk(GRAPE_KERNEL_WALK_GRAD, 0);
     HIPCHECK(grape_walk::launch_merged_wide(1, Pw[0], Bw[0], Pw[1], Bw[1], st));

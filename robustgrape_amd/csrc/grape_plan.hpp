@@ -160,6 +160,7 @@ struct grape_plan {
     int merge_pa = 0;
     // the wide pass (enqueue_wide): W = max_batch x nchunks evaluations per pass of a rank-one merged plan, or 0
     int wide = 0;
+    int wide_lev[2][2] = {{0, 0}, {0, 0}};  // the head's level of sector w's weighted slot, per class (k_wide_head)
     cd *d_e1_Et = nullptr, *d_e1_scr = nullptr;
     unsigned char *d_e1_tab = nullptr;  // the kernel's table blob (grape_eval1 tab_build)
     int e1_pa = 0;

@@ -751,6 +751,7 @@ static int setup_merge(PlanBuild &b) {
                 const int g = sc.sidx[(size_t)w * sc.S + r];
                 if (g >= 0 && W[g] != 0.0) {
                     Pc.rank1_c[w] = r;
+                    p->wide_lev[cl][w] = g;
                     ++n;
                 }
             }
@@ -762,7 +763,11 @@ static int setup_merge(PlanBuild &b) {
     // the wide pass: its U blocks and alphas take the chunk totals' and carries' buffers (alloc_class: at least
     // max_batch x nchunks tiles per sector of either class, class B's sized for its own, larger, chunk count)
     const long wide = (long)p->max_batch * A.nchunks;
-    if (r1 && !(P.opts & GRAPE_OPT_NO_WIDE) && grape_walk::wide_ok(A, Bq) && wide * 2 <= (long)INT_MAX) p->wide = (int)wide;
+    // (wide_ok and r1 give the wide head, k_wide_head, what it relies on: na <= 1, no x_add in H0, no error sources,
+    // one weighted level per sector, 1 + 2 sectors; d <= 12 leaves at most kWideHeadMaxFixed untouched levels)
+    if (r1 && !(P.opts & GRAPE_OPT_NO_WIDE) && grape_walk::wide_ok(A, Bq) && wide * 2 <= (long)INT_MAX &&
+        p->SH.nfixed <= grape_proj::kWideHeadMaxFixed)
+        p->wide = (int)wide;
     return GRAPE_OK;
 }
 

@@ -771,6 +771,112 @@ __global__ __launch_bounds__(kDiagBlock) void k_sec_head_diag(SectorHead H, int 
     }
 }
 
+// The wide pass's head (WideHead): k_sec_head_diag's alpha mode with one lane per evaluation.  There every sector
+// has one weighted level c and U holds column c only, so the formulas above reduce to, per evaluation,
+//   K_s = conj(u0_s) U_cc of sector s,  k_g = conj(u0_g) of an untouched level g,
+//   tau = sum_s W_s K_s + sum_g W_g k_g,   F = [sum_s W_s p_s |K_s|^2 + sum_g W_g p_g |k_g|^2 + |tau|^2] / DD,
+//   alpha_s = (2 / DD) W_s conj(u0_s) (p_s conj(K_s) + conj(tau)),
+//   target part of F_dx_add: [2 (sum_s W_s p_s Re(conj(d_s) U_cc conj(K_s)) + sum_g W_g p_g Re(conj(d_g) conj(k_g)))
+//                             + 2 Re(conj(tau) (sum_s W_s conj(d_s) U_cc + sum_g W_g conj(d_g)))] / DD
+// on 3 + nfixed levels, all in one lane's registers: the operations of diag_row per element, summed in a fixed
+// order (the sectors in class order, then the untouched levels) where the row groups sum in a shuffle tree.
+// The term table, the target operators' diagonals, W and the untouched levels are the same for every lane and
+// come through the constant address space (scalar loads); no LDS, no barrier.  (k_sec_head_diag served the wide
+// pass with 8 lanes, a staging pass of every table and 17 complex U entries per evaluation: 0.12 ms of a 2.0-ms
+// C2 step.)
+template <class T>
+using cptr = const __attribute__((address_space(4))) T *;
+constexpr int kWideHeadBlock = 64, kWideHeadLevels = 3 + kWideHeadMaxFixed;
+__global__ __launch_bounds__(kWideHeadBlock) void k_wide_head(WideHead H, int nb) {
+    const grape::DevProblem &P = H.P;
+    const long gl = (long)blockIdx.x * kWideHeadBlock + threadIdx.x;
+    if (gl >= (long)nb) return;
+    const size_t b = (size_t)gl;
+    const double *xb = H.x + b * P.nx, *xadd = xb + (size_t)P.np * P.Nt;
+    const cptr<double> Wc = (cptr<double>)P.W;
+    const cptr<int> fx = (cptr<int>)H.fixed;
+    const cptr<cd> ops = (cptr<cd>)P.ops;
+    const cptr<grape::Term> terms = (cptr<grape::Term>)P.tgt;
+    constexpr int NL = kWideHeadLevels;
+    int g[NL];  // the levels in the order of the sums; -1: none (launch-uniform, as every table value below)
+    double W[NL];
+#pragma unroll
+    for (int l = 0; l < NL; ++l) {
+        g[l] = l < 3 ? H.lev[l] : (l - 3 < H.nfixed ? fx[l - 3 < H.nfixed ? l - 3 : 0] : -1);
+        W[l] = g[l] >= 0 ? Wc[g[l]] : 0.0;
+    }
+    // the target's diagonal on these levels at x_add (u0) and, for na = 1, at x_add + eps e_0 (u1): target_entry's sums
+    cd u0[NL], u1[NL];
+#pragma unroll
+    for (int l = 0; l < NL; ++l) u0[l] = u1[l] = cd{0.0, 0.0};
+    const grape::Pert none = no_pert(), pq = xadd_pert(P, 0);
+    for (int q = 0; q < P.n_tgt; ++q) {
+        grape::Term tm;
+        tm.op = terms[q].op;
+        tm.var = terms[q].var;
+        tm.index = terms[q].index;
+        tm.func = terms[q].func;
+        tm.a = terms[q].a;
+        tm.b = terms[q].b;
+        tm.sre = terms[q].sre;
+        tm.sim = terms[q].sim;
+        const cd c0 = grape::term_coef(tm, 1, xb, xadd, none);
+        const cd c1 = P.na ? grape::term_coef(tm, 1, xb, xadd, pq) : c0;
+#pragma unroll
+        for (int l = 0; l < NL; ++l) {
+            if (g[l] < 0) continue;
+            const size_t at = ((size_t)tm.op * P.D + g[l]) * P.D + g[l];
+            const cd o{ops[at].re, ops[at].im};
+            u0[l] = cadd(u0[l], cmul(c0, o));
+            u1[l] = cadd(u1[l], cmul(c1, o));
+        }
+    }
+    auto pd = [](double w) { return w != 0.0 ? 1.0 : 0.0; };
+    cd U[3], K[3];
+    double fsum = 0.0;
+    cd tau{0.0, 0.0};
+#pragma unroll
+    for (int s = 0; s < 3; ++s) {
+        U[s] = H.ucc[s][b];
+        K[s] = cmul(cconj(u0[s]), U[s]);
+        fsum += W[s] * pd(W[s]) * (K[s].re * K[s].re + K[s].im * K[s].im);
+        tau = cadd(tau, cscale(W[s], K[s]));
+    }
+#pragma unroll
+    for (int l = 3; l < NL; ++l) {  // U_gg = 1: K_gg = conj(u0_g)
+        if (g[l] < 0) continue;
+        const cd k = cconj(u0[l]);
+        fsum += W[l] * pd(W[l]) * (k.re * k.re + k.im * k.im);
+        tau = cadd(tau, cscale(W[l], k));
+    }
+    H.F[b] = (fsum + tau.re * tau.re + tau.im * tau.im) / P.DD;
+    const double sc = 2.0 / P.DD;
+#pragma unroll
+    for (int s = 0; s < 3; ++s) {
+        const cd f = cadd(cscale(pd(W[s]), cconj(K[s])), cd{tau.re, -tau.im});
+        H.alpha[s][b * (size_t)H.astride[s]] = cscale(sc, cscale(W[s], cmul(cconj(u0[s]), f)));
+    }
+    if (P.na) {  // target part of F_dx_add, d = (u0(x_add + eps e_0) - u0) / eps
+        double sa = 0.0;
+        cd trd{0.0, 0.0};
+#pragma unroll
+        for (int s = 0; s < 3; ++s) {
+            const cd dr = cconj(cscale(P.inv_eps, csub(u1[s], u0[s])));
+            const cd kd = cmul(dr, U[s]);
+            sa += W[s] * pd(W[s]) * (kd.re * K[s].re + kd.im * K[s].im);
+            trd = cadd(trd, cscale(W[s], kd));
+        }
+#pragma unroll
+        for (int l = 3; l < NL; ++l) {
+            if (g[l] < 0) continue;
+            const cd kd = cconj(cscale(P.inv_eps, csub(u1[l], u0[l]))), k = cconj(u0[l]);
+            sa += W[l] * pd(W[l]) * (kd.re * k.re + kd.im * k.im);
+            trd = cadd(trd, cscale(W[l], kd));
+        }
+        H.Fdx[b * P.nx + (size_t)P.np * P.Nt] = (2.0 * sa + 2.0 * (tau.re * trd.re + tau.im * trd.im)) / P.DD;
+    }
+}
+
 // The error head in the same diagonal form: with Ue = U Tot (block-diagonal, zero on the untouched
 // levels), Ke = U0^dag Ue and K = U0^dag U, k_sec_err_head's products reduce to (A = diag(w),
 // B = diag(p); FidelityCalculations.jl:78-113)
@@ -942,6 +1048,15 @@ hipError_t launch_sector_head(const SectorHead &H, int nb, hipStream_t st) {
     }
     const size_t lds = (size_t)kHeadSlots * H.P.D * H.P.D * sizeof(cd);
     hipLaunchKernelGGL(k_sec_head, dim3((unsigned)nb), dim3(SEC_BLOCK), lds, st, H);
+    return hipGetLastError();
+}
+
+hipError_t launch_wide_head(const WideHead &H, int nb, hipStream_t st) {
+    const grape::DevProblem &P = H.P;
+    if (nb < 1 || P.na > 1 || P.xadd_dep || P.ne != 0 || H.nfixed < 0 || H.nfixed > kWideHeadMaxFixed) return hipErrorInvalidValue;
+    for (int s = 0; s < 3; ++s)
+        if (H.lev[s] < 0 || H.lev[s] >= P.D || !H.ucc[s] || !H.alpha[s]) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_wide_head, dim3((unsigned)((nb + kWideHeadBlock - 1) / kWideHeadBlock)), dim3(kWideHeadBlock), 0, st, H, nb);
     return hipGetLastError();
 }
 

@@ -70,6 +70,25 @@ hipError_t launch_sector_head(const SectorHead &H, int nb, hipStream_t st);
 // group of lanes
 hipError_t launch_sector_err_head(const SectorHead &H, int nb, hipStream_t st);
 
+// The wide pass's head (grape_walk_api.hpp launch_merged_wide), one lane per evaluation, lane b = evaluation b as
+// in the wide walks: a diagonal projector and target, three sectors (one class of one, one of two) with one
+// weighted level each, na <= 1, no x_add in H0, no error sources.  Of U it needs U_cc of each sector -- entry c of
+// the forward walk's psi_N -- and writes F, alpha per sector (row c of the sector's M block is alpha U_c.: what
+// the gradient walk starts from) and the target part of F_dx_add.  Sectors in the head's class order.
+constexpr int kWideHeadMaxFixed = 5;  // untouched levels: d <= 12 less the sectors' 3 + 2 + 2
+struct WideHead {
+    grape::DevProblem P;      // the full problem, as SectorHead::P
+    int lev[3];               // level of each sector's weighted slot
+    const grape::cd *ucc[3];  // [nb]: U_cc of each sector, evaluation-minor
+    grape::cd *alpha[3];      // alpha of evaluation b at alpha[s][b * astride[s]]  (written)
+    int astride[3];
+    const int *fixed;         // levels no operator touches (U_gg = 1), nfixed <= kWideHeadMaxFixed
+    int nfixed;
+    const double *x;          // [nb][nx]
+    double *F, *Fdx;          // (written: F[b], and for na = 1 Fdx[b * nx + np * Nt])
+};
+hipError_t launch_wide_head(const WideHead &H, int nb, hipStream_t st);
+
 // the small engine's view (grape_launch.hpp)
 inline Heads small_heads(const grape::DevProblem &P, const grape::DevBatch &B) {
     Heads H{};

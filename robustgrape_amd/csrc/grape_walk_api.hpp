@@ -60,8 +60,8 @@ hipError_t launch_merged(int stage, const grape::DevProblem &PA, const grape::De
                          const grape::DevBatch &BB, hipStream_t st);
 // The wide pass of a rank-one merged plan (grape_walk.hpp, "The wide pass"): one lane per evaluation over all
 // N_t steps, BA.nb evaluations, no chunks and no scan.  Stage 0: k_walk_fwd_m<..., WIDE> walks psi = U e_c forward
-// and writes the head's U blocks (BA.Ub / BB.Ub: column c filled, the rest zero); stage 1: k_walk_grad_m<..., WIDE>
-// starts from them and the head's alpha per sector (BA.Msec / BB.Msec: [nb * nsec], SectorHead::alpha) and walks
+// and writes psi_N (BA.Ub / BB.Ub: entry j of chain ch at [(ch * D + j) * nb + b], twins one chain); stage 1:
+// k_walk_grad_m<..., WIDE> starts from it and the head's alpha per sector (BA.Msec / BB.Msec: [nb * nsec], WideHead) and walks
 // back in time, writing the F_dx rows.  Both read BA.x ([nb][nx], no transposed copy) through workgroup tiles of
 // 16 steps.  wide_ok tells whether the classes fit.
 constexpr int kWideMaxNt = 4096;

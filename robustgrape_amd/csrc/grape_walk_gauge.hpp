@@ -8,6 +8,7 @@
 // its own to mirror, and the fused form has one rounding fewer per component.
 #pragma once
 #include "grape_cis.hpp"
+#include "grape_fd_weight.hpp"
 #include "grape_walk_core.hpp"
 
 namespace grape {
@@ -91,21 +92,13 @@ __device__ __forceinline__ cd gauge_cis_tab(double t, const grape_cis::CisTabEnt
     else sincos(t, &s, &c);
     return cmake(c, s);
 }
-// e^{i phi} - 1 without cancellation: (-2 sin^2(phi / 2), sin phi); Taylor for the FD-sized
-// phases (|phi| <= 0.05: truncation below 1e-22 relative), the library otherwise
+// e^{i phi} - 1 without cancellation (grape_fd_weight.hpp, which a host compiler builds too: Taylor for the
+// FD-sized phases, the library otherwise)
 // (round 5: Horner in t^2 with the reciprocal factorials as constants -- the quotient form spent
 // 8 double divisions per step, ~7 % of the merged gradient walk's VALU instructions)
-__device__ __forceinline__ double sin_small(double t) {  // sin t, |t| <= 0.05: Taylor to t^9
-    const double t2 = t * t;
-    return t * fma(t2, fma(t2, fma(t2, fma(t2, 1.0 / 362880.0, -1.0 / 5040.0), 1.0 / 120.0), -1.0 / 6.0), 1.0);
-}
 __device__ __forceinline__ cd cis_m1(double phi) {
-    if (fabs(phi) <= 0.05) {
-        const double sh = sin_small(0.5 * phi);
-        return cmake(-2.0 * sh * sh, sin_small(phi));
-    }
-    const double sh = sin(0.5 * phi);
-    return cmake(-2.0 * sh * sh, sin(phi));
+    const grape_fd::Z q = grape_fd::cis_m1(phi);
+    return cmake(q.re, q.im);
 }
 // the difference weights of (E' - E)_rj = E_rj f_rj, formed once per pair r < j (f_jr = conj(f_rj) bit for bit),
 // straight from the charge differences: f_rj = e^{i phi (N_r - N_j)} - 1 = rho(N_r - N_j) with

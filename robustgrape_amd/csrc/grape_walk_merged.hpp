@@ -178,15 +178,12 @@ __device__ __forceinline__ void wide_step_frame(const cd *Et, cd (&chi)[NE][D]) 
         for (int j = 0; j < D; ++j) chi[w][j] = t[j];
     }
 }
-// the head's U block of one sector from psi_N: column c filled, the rest zero (the head's sums weight every
-// other entry with zero, which must not meet a NaN)
+// psi_N of one chain for the head (k_wide_head reads entry c: U_cc) and the gradient walk's start, evaluation-minor:
+// entry j at u[j * nbe] (u: the chain's first entry of this evaluation), so a wave's stores and loads are contiguous
 template <int D>
-__device__ __forceinline__ void wide_store_u(cd *u, int c, const cd (&psi)[D]) {
+__device__ __forceinline__ void wide_store_psi(cd *u, size_t nbe, const cd (&psi)[D]) {
 #pragma unroll
-    for (int j = 0; j < D; ++j) {
-#pragma unroll
-        for (int i = 0; i < D; ++i) u[j * D + i] = i == c ? psi[j] : czero();
-    }
+    for (int j = 0; j < D; ++j) u[j * nbe] = psi[j];
 }
 // The controls of the workgroup's kWalkBlock evaluations over one tile of kFdxTile steps, [row][step] in LDS:
 // sixteen lanes read one row's 128-byte piece per instruction, so every line of x is fetched once and used
@@ -299,10 +296,10 @@ __device__ __forceinline__ void wide_fwd_body(const DevProblem &PA, const DevBat
         wide_reframe<2, NEB>(pw, psiB);
     }
     if (L.ok) {
-        wide_store_u<DA>(BA.Ub + (size_t)L.be * DA * DA, cA, psiA[0]);
+        wide_store_psi<DA>(BA.Ub + L.be, (size_t)L.nbe, psiA[0]);
 #pragma unroll
-        for (int w = 0; w < 2; ++w)  // (twins: both sectors' U from the one chain)
-            wide_store_u<2>(BB.Ub + ((size_t)L.be * 2 + w) * 4, PB.rank1_c[w], psiB[TWB ? 0 : w]);
+        for (int w = 0; w < NEB; ++w)  // (twins: one chain serves both sectors)
+            wide_store_psi<2>(BB.Ub + (size_t)w * 2 * L.nbe + L.be, (size_t)L.nbe, psiB[w]);
     }
 }
 template <int DA, bool TWB, bool LAD, bool WIDE = false>
@@ -734,9 +731,13 @@ __device__ __forceinline__ void merged_r1_init(const cd *ca, size_t nbe, const c
 // (The diagonal v_jj enter only phi's column sum; as a complex MAC onto the off-diagonal terms they are 10 F64
 // instructions fewer per step and lane, which bought 0.8 % of the gradient walk and nothing that the bench could
 // tell from its run-to-run spread: DESIGN.md 9.)
-template <int D, int NE, int NSEC, bool LAD>
-__device__ __forceinline__ double wide_step_grad(const cd *Et, const GaugeN<D> (&gn)[NE], cd p1, cd q, double inv_eps,
+// The difference weights come in formed (wide_fd_weights): rh[m] = rho(m) for ladder charges, fw[we] the pair
+// weights of propagator we otherwise.
+template <int D, int NE, int NSEC, bool LAD, int DR>
+__device__ __forceinline__ double wide_step_grad(const cd *Et, const GaugeN<D> (&gn)[NE], cd p1, const cd (&rh)[DR],
+                                                 const cd (&fw)[NE][kGaugePairs<D>], double inv_eps,
                                                  cd (&psi)[NSEC][D], cd (&phi)[NSEC][D]) {
+    static_assert(D <= DR, "weights up to the sector's highest charge difference");
     constexpr int NSH = NSEC / NE;
     MStore<D, false> E[NE];
 #pragma unroll
@@ -746,15 +747,9 @@ __device__ __forceinline__ double wide_step_grad(const cd *Et, const GaugeN<D> (
         else gauge_phases<D>(p1, gn[w], dph);
         gauge_prop_lds<D, true>(Et + w * D * D, dph, E[w]);
     }
-    cd rh[D];
-    if constexpr (LAD) ladder_rho<D>(q, rh);
     double tot = 0.0, one = 0.0;
 #pragma unroll
     for (int we = 0; we < NE; ++we) {
-        cd fw[kGaugePairs<D>];
-        if constexpr (!LAD) {
-            gauge_fd_weights_dn<D>(q, gn[we], fw);
-        }
 #pragma unroll
         for (int t = 0; t < NSH; ++t) {
             const int w = we * NSH + t;
@@ -804,7 +799,7 @@ __device__ __forceinline__ double wide_step_grad(const cd *Et, const GaugeN<D> (
 #pragma unroll
                     for (int j = 0; j < D; ++j) {
                         if (r == j) continue;
-                        const cd z = cmulf(v[r][j], pm[j]), g = gauge_fd_weight<D>(fw, r, j);
+                        const cd z = cmulf(v[r][j], pm[j]), g = gauge_fd_weight<D>(fw[we], r, j);
                         c = fma(z.re, g.re, c);
                         c = fma(-z.im, g.im, c);
                     }
@@ -825,14 +820,103 @@ __device__ __forceinline__ double wide_step_grad(const cd *Et, const GaugeN<D> (
     }
     return NSEC > 1 ? tot : one;
 }
-// the wide gradient walk's start of one sector: psi_N = column c of the head's U block, phi_N = conj(alpha) e_c
-// (alpha: the head's factor of row c of M, grape_projector.hip diag_row; summed over a twin pair: a2)
+// The wide gradient walk's difference weights (grape_fd_weight.hpp): the per-step phase a ((x_k + eps) - x_k) is
+// a eps up to the rounding of x_k + eps, so the weights at phi0 = fl(a eps) are formed once per kernel -- by cis_m1
+// and the recurrences the other walks run per step -- and a step adds the first-order term in dh = h - eps,
+// h = (x_k + eps) - x_k: two FMAs per weight where cis_m1 and the recurrence take 28 VALU instructions.  h == eps
+// gives dh = 0 and the per-step form's bits; a |dh| above the guard's bound (fd_threshold_h) takes the per-step form
+// itself, in a divergent branch.  The base is the same in every lane: rho0 and the bound are wave-uniform scalars.
+// An FMA reads one scalar operand, so the twin ladder form keeps its four derivative factors in vector registers (as
+// scalars each is moved per use: 4 VALU instructions a step); the other forms hold them as scalars too and pay the
+// moves (in vector registers they put the walk into scratch: 12 bytes a lane without twins, more with general
+// charges' ten factors).
+// Weights: ladder charges m = 1 .. DA - 1 (class B's one pair is m = 1); otherwise class A's pairs, then one pair per
+// propagator of class B, each from its runtime charge difference.
+__device__ __forceinline__ double wide_uniform(double v) {
+    const int lo = __builtin_amdgcn_readfirstlane(__double2loint(v)), hi = __builtin_amdgcn_readfirstlane(__double2hiint(v));
+    return __hiloint2double(hi, lo);
+}
+template <int DA, int NEB, bool LAD>
+struct WideFd {
+    static constexpr int NW = LAD ? DA - 1 : kGaugePairs<DA> + NEB;
+    double eps, thr;       // the guard: |h - eps| <= thr
+    grape_fd::Base b[NW];  // rho0 and a g (fd_base_h)
+};
+template <int DA, int NEB, bool LAD>
+__device__ __forceinline__ void wide_fd_base(double a, double eps, const GaugeN<DA> (&gA)[1], const GaugeN<2> (&gB)[NEB],
+                                             WideFd<DA, NEB, LAD> &fd) {
+    static_assert(DA >= 2, "class B's pair reads rho(1)");
+    const cd q0 = cis_m1(a * eps);
+    int mmax = 0;
+    auto take = [&](int i, cd f, int dn) {
+        const grape_fd::Base b = grape_fd::fd_base_h(grape_fd::fd_base_signed(grape_fd::Z{f.re, f.im}, dn), a);
+        fd.b[i].rho0 = grape_fd::Z{wide_uniform(b.rho0.re), wide_uniform(b.rho0.im)};
+        fd.b[i].g = (LAD && NEB == 1) ? b.g : grape_fd::Z{wide_uniform(b.g.re), wide_uniform(b.g.im)};
+        mmax = max(mmax, dn < 0 ? -dn : dn);
+    };
+    if constexpr (LAD) {
+        cd rh0[DA];
+        ladder_rho<DA>(q0, rh0);
+#pragma unroll
+        for (int m = 1; m < DA; ++m) take(m - 1, rh0[m], m);
+    } else {
+        cd f0[kGaugePairs<DA>], f1[1];
+        gauge_fd_weights_dn<DA>(q0, gA[0], f0);
+#pragma unroll
+        for (int r = 0; r < DA; ++r) {
+#pragma unroll
+            for (int j = r + 1; j < DA; ++j) take(gauge_pair(DA, r, j), f0[gauge_pair(DA, r, j)], gA[0].n[r] - gA[0].n[j]);
+        }
+#pragma unroll
+        for (int w = 0; w < NEB; ++w) {
+            gauge_fd_weights_dn<2>(q0, gB[w], f1);
+            take(kGaugePairs<DA> + w, f1[0], gB[w].n[0] - gB[w].n[1]);
+        }
+    }
+    fd.eps = eps;
+    fd.thr = wide_uniform(grape_fd::fd_threshold_h(a, eps, mmax));
+}
+template <int DA, int NEB, bool LAD>
+__device__ __forceinline__ void wide_fd_weights(const WideFd<DA, NEB, LAD> &fd, double a, double h, const GaugeN<DA> (&gA)[1],
+                                                const GaugeN<2> (&gB)[NEB], cd (&rh)[DA], cd (&fwA)[1][kGaugePairs<DA>],
+                                                cd (&fwB)[NEB][1]) {
+    const double dh = h - fd.eps;
+    auto at = [&](int i) {
+        const grape_fd::Z z = grape_fd::fd_step(fd.b[i], dh);
+        return cmake(z.re, z.im);
+    };
+    if (fabs(dh) <= fd.thr) {
+        if constexpr (LAD) {
+            rh[0] = czero();
+#pragma unroll
+            for (int m = 1; m < DA; ++m) rh[m] = at(m - 1);
+        } else {
+#pragma unroll
+            for (int i = 0; i < kGaugePairs<DA>; ++i) fwA[0][i] = at(i);
+#pragma unroll
+            for (int w = 0; w < NEB; ++w) fwB[w][0] = at(kGaugePairs<DA> + w);
+        }
+    } else {  // the per-step form: x_k + eps rounded to x_k or to x_k + 2 eps, a NaN, or no bound for this a eps
+        const cd q = cis_m1(a * h);
+        if constexpr (LAD) {
+            ladder_rho<DA>(q, rh);
+        } else {
+            gauge_fd_weights_dn<DA>(q, gA[0], fwA[0]);
+#pragma unroll
+            for (int w = 0; w < NEB; ++w) gauge_fd_weights_dn<2>(q, gB[w], fwB[w]);
+        }
+    }
+}
+// the wide gradient walk's start of one sector: psi_N as the forward walk left it (wide_store_psi),
+// phi_N = conj(alpha) e_c (alpha: the head's factor of row c of M, grape_projector.hip k_wide_head; summed over a
+// twin pair: a2)
 template <int D>
-__device__ __forceinline__ void wide_grad_init(const cd *u, const cd *a, const cd *a2, int c, cd (&psi)[D], cd (&phi)[D]) {
+__device__ __forceinline__ void wide_grad_init(const cd *u, size_t nbe, const cd *a, const cd *a2, int c, cd (&psi)[D],
+                                               cd (&phi)[D]) {
     const cd al = cconj(a2 ? cadd(*a, *a2) : *a);
 #pragma unroll
     for (int j = 0; j < D; ++j) {
-        psi[j] = u[j * D + c];
+        psi[j] = u[j * nbe];
         phi[j] = j == c ? al : czero();
     }
 }
@@ -846,22 +930,28 @@ __device__ __forceinline__ void wide_grad_body(const DevProblem &PA, const DevBa
     frow[threadIdx.x] = make_int2(L.ok ? L.be : -1, 0);
     cd psiA[1][DA], phiA[1][DA], psiB[NXB][2], phiB[NXB][2];
     const size_t be = (size_t)L.be;
-    wide_grad_init<DA>(BA.Ub + be * DA * DA, BA.Msec + be, nullptr, PA.rank1_c[0], psiA[0], phiA[0]);
+    const size_t nbe = (size_t)L.nbe;
+    wide_grad_init<DA>(BA.Ub + be, nbe, BA.Msec + be, nullptr, PA.rank1_c[0], psiA[0], phiA[0]);
 #pragma unroll
     for (int w = 0; w < NXB; ++w) {  // (twin sum: alpha_0 + alpha_1, both sectors' level at one index)
         const cd *ab = BB.Msec + be * 2 + w;
-        wide_grad_init<2>(BB.Ub + (be * 2 + w) * 4, ab, NXB == 1 ? ab + 1 : nullptr, PB.rank1_c[w], psiB[w], phiB[w]);
+        wide_grad_init<2>(BB.Ub + (size_t)(TWB ? 0 : w) * 2 * nbe + be, nbe, ab, NXB == 1 ? ab + 1 : nullptr, PB.rank1_c[w],
+                          psiB[w], phiB[w]);
     }
     GaugeN<DA> gA[1];
     GaugeN<2> gB[NEB];
     gA[0] = gauge_charges<DA>(PA, 0);
 #pragma unroll
     for (int w = 0; w < NEB; ++w) gB[w] = gauge_charges<2>(PB, w);
+    WideFd<DA, NEB, LAD> fd;
+    wide_fd_base<DA, NEB, LAD>(PA.gauge_a, PA.eps, gA, gB, fd);
     auto step = [&](double xk) {  // one step of both classes: the F_dx value, in the plan's class order
         const double xe = xk + PA.eps;
-        const cd p1 = gauge_cis_tab(PA.gauge_a * xk, ctab), q = cis_m1(PA.gauge_a * (xe - xk));
-        const double sa = wide_step_grad<DA, 1, 1, LAD>(PA.gauge_Et, gA, p1, q, PA.inv_eps, psiA, phiA);
-        const double sb = wide_step_grad<2, NEB, NXB, LAD>(PB.gauge_Et, gB, p1, q, PB.inv_eps, psiB, phiB);
+        const cd p1 = gauge_cis_tab(PA.gauge_a * xk, ctab);
+        cd rh[DA], fwA[1][kGaugePairs<DA>], fwB[NEB][1];
+        wide_fd_weights<DA, NEB, LAD>(fd, PA.gauge_a, xe - xk, gA, gB, rh, fwA, fwB);  // (xe - xk: exact)
+        const double sa = wide_step_grad<DA, 1, 1, LAD>(PA.gauge_Et, gA, p1, rh, fwA, PA.inv_eps, psiA, phiA);
+        const double sb = wide_step_grad<2, NEB, NXB, LAD>(PB.gauge_Et, gB, p1, rh, fwB, PB.inv_eps, psiB, phiB);
         return sa + sb;  // (the classes' parts in either order: see k_walk_grad_m's step)
     };
     // The tiles and the steps of a tile in descending order.  One workgroup tile serves both ways: it arrives
