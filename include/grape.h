@@ -61,8 +61,10 @@ typedef enum grape_status {
  * GRAPE_MAX_DENSE_DIM < ndim <= GRAPE_MAX_TILED_DIM (zero-padded to a multiple of 16).  It serves
  * grape_fidelity_grad, grape_fidelity_grad_device_async and grape_expm_batch for operator-basis
  * problems with a Hermitian H0 (terms on 1, x or the step index), a diagonal projector, a target
- * that may read x_add, and no error sources.  Refused there with GRAPE_ERR_UNSUPPORTED at plan
- * creation: error sources, H0 terms that read x_add, a non-diagonal projector,
+ * that may read x_add, and -- on a plan created with GRAPE_OPT_TILED_ERR -- Hermitian error sources
+ * whose terms sit on 1, x or the step index (F_d2err, F_d2err_dx as the dense engine lays them out).
+ * Refused there with GRAPE_ERR_UNSUPPORTED at plan creation: error sources without that option, H0 or
+ * error terms that read x_add, a non-Hermitian error generator, a non-diagonal projector,
  * GRAPE_OPT_GENERAL_H0 / a non-Hermitian H0, GRAPE_DESC_HOST_TABLES; on a tiled plan: the
  * analysis entry points (grape_unitary_derivs, the interaction operators, the expectation
  * values) and the time slices.  A tiled plan sizes the evaluations of one pass by a byte budget
@@ -264,6 +266,12 @@ typedef struct grape_desc {
  * rounding (F 1e-12, F_dx 1e-11 max|F_dx| + 1e-13), not bit for bit; a repeated call repeats its bits.
  * This option keeps the chunked passes for every call (grape_plan_wide tells W). */
 #define GRAPE_OPT_NO_WIDE 131072
+/* Error sources on the tiled engine (an addition within ABI 12: this option bit): with it a plan of
+ * GRAPE_MAX_DENSE_DIM < ndim <= GRAPE_MAX_TILED_DIM takes nerr > 0 and returns F_d2err and F_d2err_dx
+ * (grape_tiled.hip, DESIGN.md 7.3 "Error sources").  Each source is Hermitian, its terms sit on 1, x or
+ * the step index, and the H0 term count plus the largest source's term count is at most 256.  Without
+ * the option such a descriptor is refused as before; at ndim <= GRAPE_MAX_DENSE_DIM the option is ignored. */
+#define GRAPE_OPT_TILED_ERR 262144
 
 typedef struct grape_plan grape_plan;
 

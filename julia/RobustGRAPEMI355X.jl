@@ -207,6 +207,7 @@ const GRAPE_DESC_HOST_TABLES = Int32(1)
 const GRAPE_OPT_GENERAL_H0 = Int32(64)   # include/grape.h: the LU-inverted chain (UnitaryCalculations.jl:47)
 const GRAPE_OPT_NO_RANK1 = Int32(65536)  # include/grape.h: the merged gradient walk keeps its matrix state
 const GRAPE_OPT_NO_WIDE = Int32(131072)  # include/grape.h: device-resident calls keep the chunked passes
+const GRAPE_OPT_TILED_ERR = Int32(262144)  # include/grape.h: error sources on the tiled engine (65-128 levels)
 
 # Closure fallback (grape.h GRAPE_DESC_HOST_TABLES): no operator basis in the descriptor.  The host
 # sees H0 only as tables, so `general` (a non-Hermitian nominal H0, e.g. a -iΓ/2 decay term:

@@ -198,6 +198,8 @@ static int enqueue(grape_plan *p, int nb, const double *d_x, double *d_F, double
         TB.x = d_x;
         TB.F = d_F;
         TB.Fdx = d_Fdx;
+        TB.Fd2 = d_Fd2;  // (error sources, GRAPE_OPT_TILED_ERR: null otherwise)
+        TB.Fd2dx = d_Fd2dx;
         HIPCHECK(grape_tiled::launch_pipeline(p->TP, TB, st, mk));
         return GRAPE_OK;
     }

@@ -440,7 +440,8 @@ int validate_desc(const grape_desc *desc, int *n_err_terms) {
         if (tables)
             return fail(GRAPE_ERR_UNSUPPORTED, "ndim > GRAPE_MAX_DENSE_DIM: closures (host tables) are served up to "
                                                "GRAPE_MAX_DENSE_DIM levels");
-        if (desc->nerr > 0)
+        const bool tiled_err = (desc->reserved[1] & GRAPE_OPT_TILED_ERR) != 0;
+        if (desc->nerr > 0 && !tiled_err)
             return fail(GRAPE_ERR_UNSUPPORTED, "ndim > GRAPE_MAX_DENSE_DIM: error sources are served up to "
                                                "GRAPE_MAX_DENSE_DIM levels");
         if (desc->reserved[1] & GRAPE_OPT_GENERAL_H0)
@@ -502,11 +503,28 @@ int choose_route(const grape_desc *desc, int n_err_terms, Route &rt) {
     // launch_table_variants).  Without the option nothing changes: a non-Hermitian H0 or error source
     // is refused above.
     rt.pivot = rt.general_h0 && D > GRAPE_MAX_SMALL_DIM;
-    if (D > GRAPE_MAX_DENSE_DIM) {  // the tiled engine (validate_desc refused closures, error sources, the general option)
+    if (D > GRAPE_MAX_DENSE_DIM) {  // the tiled engine (validate_desc refused closures, the general option, and error
+                                    // sources without GRAPE_OPT_TILED_ERR)
         for (int k = 0; k < desc->n_h0_terms; ++k)
             if (desc->h0_terms[k].var == GRAPE_VAR_XADD)
                 return fail(GRAPE_ERR_UNSUPPORTED, "ndim > GRAPE_MAX_DENSE_DIM: H0 terms that read x_add are served up "
                                                    "to GRAPE_MAX_DENSE_DIM levels");
+        // error sources (GRAPE_OPT_TILED_ERR, let through by validate_desc): Hermitian, off x_add, and few enough
+        // terms that a variant's coefficients -- H0's, then one source's -- are staged in LDS together
+        int most = 0;
+        for (int e = 0; e < desc->nerr; ++e) {
+            const grape_term *t = desc->err_terms + desc->err_term_offsets[e];
+            const int n = desc->err_term_offsets[e + 1] - desc->err_term_offsets[e];
+            for (int k = 0; k < n; ++k)
+                if (t[k].var == GRAPE_VAR_XADD)
+                    return fail(GRAPE_ERR_UNSUPPORTED, "ndim > GRAPE_MAX_DENSE_DIM: error terms that read x_add are "
+                                                       "served up to GRAPE_MAX_DENSE_DIM levels");
+            if (int rc = check_hermitian_terms(desc, t, n, "error source (tiled engine)")) return rc;
+            most = std::max(most, n);
+        }
+        if (desc->nerr > 0 && desc->n_h0_terms + most > grape_tiled::kMaxTerms)
+            return fail(GRAPE_ERR_UNSUPPORTED, "ndim > GRAPE_MAX_DENSE_DIM: more than 256 terms in H0 and one error "
+                                               "source together");
         if (desc->projector) {
             const size_t n = (size_t)D;
             for (size_t j = 0; j < n; ++j)

@@ -255,7 +255,9 @@ void from_tiled_image(const double *img, int d, double *dst) {
 // A tiled plan's workspace is sized by bytes, not by max_batch x everything: a quarter of the budget (at most
 // kTiledSlabItems items) holds the slab of the exponential and of the gradient's eps-variants, the rest the
 // evaluations of one pass (E and Q: 2 N_t images each, 512 MB at P = 128, N_t = 1 024).  A call of more
-// evaluations than fit runs as several passes with identical arithmetic.
+// evaluations than fit runs as several passes with identical arithmetic.  With error sources the same budget
+// also holds every step's local-frame images (grape_tiled_api.hpp err_eval_images: 1.25 GB more per evaluation
+// at that size with np = 2, ne = 1) and np + 1 more images per slab item.
 constexpr size_t kTiledBudgetBytes = (size_t)6 << 30;
 constexpr size_t kTiledSlabItems = 1024;
 constexpr size_t kTiledSlabImages = 9;  // A, A^2, A^3, A^4, two Horner buffers, E', Q_{k-1} M'_c, Y^dag
@@ -279,9 +281,13 @@ int create_tiled(const grape_desc *desc, grape_plan *p, const ProjectorSetup &ps
     grape_tiled::TiledProblem &TP = p->TP;
     DevProblem &P = TP.P;
     fill_problem_scalars(desc, ps.trP, P);
-    const std::vector<grape::VSpec> vs = set_variants(P, 0, false);  // nominal only: the eps-variants are never kept
-    P.nv = 1;
+    // the nominal alone is kept; with error sources (GRAPE_OPT_TILED_ERR) the list is the dense engine's, and
+    // launch_pipeline exponentiates its variants slab by slab into the local-frame images
+    const int ne = desc->nerr;
+    const std::vector<grape::VSpec> vs = set_variants(P, 0, ne > 0);
+    P.nv = ne > 0 ? (int)vs.size() : 1;
     P.nvg = P.np;
+    P.nz = ne > 0 ? P.np + ne + ne * P.np : 0;
     TP.Pd = grape_tiled::padded_dim(D);
     // scan chunking: ~sqrt(N_t) chunks, as the dense engine
     const int nc = (int)std::ceil(std::sqrt((double)P.Nt));
@@ -289,10 +295,14 @@ int create_tiled(const grape_desc *desc, grape_plan *p, const ProjectorSetup &ps
     TP.Nc = (P.Nt + TP.Lc - 1) / TP.Lc;
     const size_t IMG = grape_tiled::image_doubles(D), imgB = IMG * sizeof(double);
     const size_t Nt = P.Nt, Nc = TP.Nc, nh = 1 + (size_t)P.na;
-    const size_t eval_imgs = 2 * Nt + 3 * Nc + 4 + 2 * nh;
-    size_t slab = std::min<size_t>(kTiledSlabItems, std::max<size_t>(1, kTiledBudgetBytes / 4 / (kTiledSlabImages * imgB)));
+    // error sources: the local-frame images of every step are stored (np + ne + ne np per step), not recomputed
+    // from a second round of variant exponentials, and the slab holds the eps2-variants of its steps
+    const size_t NE = ne, NP = P.np;
+    const size_t eval_imgs = 2 * Nt + 3 * Nc + 4 + 2 * nh + grape_tiled::err_eval_images(Nt, Nc, NP, P.na, NE);
+    const size_t slab_imgs = kTiledSlabImages + grape_tiled::err_slab_images(NP, NE);
+    size_t slab = std::min<size_t>(kTiledSlabItems, std::max<size_t>(1, kTiledBudgetBytes / 4 / (slab_imgs * imgB)));
     slab = std::min(slab, (size_t)p->max_batch * Nt);
-    const size_t slabB = slab * kTiledSlabImages * imgB;
+    const size_t slabB = slab * slab_imgs * imgB;
     const size_t fit = kTiledBudgetBytes > slabB ? (kTiledBudgetBytes - slabB) / (eval_imgs * imgB) : 0;
     if (fit < 1)
         return fail(GRAPE_ERR_ALLOC, "tiled engine: one evaluation needs " + std::to_string(eval_imgs * imgB + slabB) +
@@ -312,6 +322,16 @@ int create_tiled(const grape_desc *desc, grape_plan *p, const ProjectorSetup &ps
               alloc_exp_slab(p->mem, slab, IMG, B.X, extra, 3) == hipSuccess &&
               p->mem.alloc(&p->d_x, MB * P.nx) == hipSuccess && p->mem.alloc(&p->d_F, MB) == hipSuccess &&
               p->mem.alloc(&p->d_Fdx, MB * P.nx) == hipSuccess && p->mem.alloc(&p->d_ctrl, kCtrlInts) == hipSuccess;
+    if (ok && ne > 0) {
+        const size_t bec = MB * NE * Nc * IMG, be = MB * NE * IMG;
+        double **per_chunk[10] = {&B.Sd, &B.Tmp, &B.Vc, &B.Sx, &B.Dx, &B.Mce, &B.Tce, &B.Dce, &B.Bst, &B.Lam};
+        double **per_src[5] = {&B.Tot, &B.Ue, &B.UeU, &B.KW, &B.Me};
+        for (double **q : per_chunk) ok = ok && p->mem.alloc(q, bec) == hipSuccess;
+        for (double **q : per_src) ok = ok && p->mem.alloc(q, be) == hipSuccess;
+        ok = ok && p->mem.alloc(&B.Zl, MB * Nt * (size_t)P.nz * IMG) == hipSuccess &&
+             p->mem.alloc(&B.Ke, be * nh) == hipSuccess && p->mem.alloc(&B.taue, 2 * MB * NE) == hipSuccess &&
+             p->mem.alloc(&B.Eh, (NP + 1) * slab * IMG) == hipSuccess && p->mem.alloc(&p->d_Fd2, MB * NE) == hipSuccess && p->mem.alloc(&p->d_Fd2dx, MB * NE * P.nx) == hipSuccess;
+    }
     if (!ok) return fail(GRAPE_ERR_ALLOC, "device allocation failed (tiled)");
     B.Ev = extra[0];
     B.Ts = extra[1];
@@ -326,7 +346,8 @@ int create_tiled(const grape_desc *desc, grape_plan *p, const ProjectorSetup &ps
         hipMemcpy(opimg, img.data(), img.size() * sizeof(double), hipMemcpyHostToDevice) != hipSuccess ||
         hipMemcpy(W, Wp.data(), Wp.size() * sizeof(double), hipMemcpyHostToDevice) != hipSuccess)
         return fail(GRAPE_ERR_HIP, "upload failed (tiled)");
-    if (int rc = upload_terms(p, desc, 0, vs, P, " (tiled)", " (tiled)")) return rc;
+    if (int rc = upload_terms(p, desc, ne > 0 ? desc->err_term_offsets[ne] : 0, vs, P, " (tiled)", " (tiled error terms)"))
+        return rc;
     TP.opimg = opimg;
     TP.W = W;
     P.W = W;

@@ -51,7 +51,27 @@ struct TiledBatch {
     int *h_smax;      // ... its pinned copy (one word read back per pass)
     double *F;        // [nb]
     double *Fdx;      // [nb][nx]
+    // error sources (P.ne > 0, GRAPE_OPT_TILED_ERR; null otherwise).  Local-frame images are kept conjugate-
+    // transposed (Zd = Z^dag), so that every trace against them is an elementwise sum and W enters the
+    // products through op()
+    double *Zl;       // [nb][Nt][nz]   Z1_u^dag (np) | W_e^dag (ne) | Z2_{e,u}^dag (ne x np), nz = np + ne + ne np
+    double *Sd, *Tmp; // [nb][ne][Nc]   (sum of W over the chunk)^dag, c >= 1; the first product of a pair
+    double *Vc, *Sx, *Dx;     // [nb][ne][Nc]  Carry^dag (sum W) Carry, its exclusive prefix S_c, Tot - S_c
+    double *Mce, *Tce, *Dce;  // [nb][ne][Nc]  Carry (M_e | S_c | Tot - S_c) Carry^dag, c >= 1 (c = 0: the images themselves)
+    double *Bst, *Lam;        // [nb][ne][Nc]  the walk's state B_k and -Lambda_k
+    double *Tot, *Ue, *UeU, *KW, *Me;  // [nb][ne] each: Tot, U Tot, Ue^dag U, Ke^dag W K, M_e = G_e U
+    double *Ke;       // [nb][ne][1 + na]  U0^dag Ue, dU0_q^dag Ue
+    double *taue;     // [nb][ne][2]       tau_e = tr(W Ke)
+    double *Eh;       // [np + 1][slab]   held eps2-variants of the current slab: x + eps2 e_u (np), then source e
+    double *Fd2;      // [nb][ne]
+    double *Fd2dx;    // [nb][ne][nx]
 };
+
+// images per evaluation / per slab item that the error path adds to a plan's workspace (grape_plan_build.hip)
+inline size_t err_eval_images(size_t Nt, size_t Nc, size_t np, size_t na, size_t ne) {
+    return ne ? Nt * (np + ne + ne * np) + ne * (10 * Nc + 5 + 1 + na) : 0;
+}
+inline size_t err_slab_images(size_t np, size_t ne) { return ne ? np + 1 : 0; }
 
 // Pipeline of one pass on `st` (the dense engine's stages and timing slots).  Reads one word back
 // (the pass's largest squaring count) after the step norms: the call synchronises `st` once.

@@ -15,7 +15,7 @@ from collections import OrderedDict
 import numpy as np
 
 from . import _capi
-from .operators import OPT_GENERAL_H0, DescriptorBuffers, TableDescriptor, has_operator_basis
+from .operators import OPT_GENERAL_H0, OPT_TILED_ERR, DescriptorBuffers, TableDescriptor, has_operator_basis
 from .tables import SharedTables, get_workers, host_tables, is_hermitian_h0, table_batch_cap, table_shapes
 from .types import FidelityRobustGRAPEProblem, split_x
 
@@ -34,7 +34,8 @@ class GrapePlan:
         plan-creation choices between implementations of the same outputs (include/grape.h).
         general_fallback: at 12 < ndim <= 64 a problem the default plan refuses or cannot serve (a
         non-Hermitian H0 or error generator) moves to the general path with the pivoted dense
-        exponential (OPT_GENERAL_H0) instead of raising.  Default: False, except inside get_plan."""
+        exponential (OPT_GENERAL_H0) instead of raising; at 64 < ndim <= 128 a problem refused for its error
+        sources alone is created once more with OPT_TILED_ERR.  Default: False, except inside get_plan."""
         if general_fallback is None:
             general_fallback = getattr(_plan_defaults, "general_fallback", False)
         L = _capi.lib()
@@ -48,6 +49,8 @@ class GrapePlan:
         self.requested_batch = self.max_batch  # before the closure-table byte cap (get_plan's key)
         self.options = int(options)
         self.general_fallback = bool(general_fallback) and 12 < self.up.ndim <= 64
+        # the same request above 64 levels: error sources move to the tiled engine's error path (OPT_TILED_ERR)
+        tiled_err_fallback = bool(general_fallback) and self.up.ndim > 64 and self.nerr > 0
         self.lock = threading.Lock()  # one evaluation at a time (the plan's buffers are shared)
         self._shared = None  # closure fallback: double-buffered shared-memory tables
         # operator bases -> the fused device path; plain closures -> the host-table fallback
@@ -64,6 +67,12 @@ class GrapePlan:
         if rc == _capi.ERR_UNSUPPORTED and self.general_fallback and not (self.options & OPT_GENERAL_H0):
             # refused as it stands (non-Hermitian H0 or error source above 12 levels): once more, general
             self.options |= OPT_GENERAL_H0
+            self._bufs.desc.reserved[1] = self.options
+            rc = L.grape_plan_create(ctypes.byref(self._bufs.desc), self.device, ctypes.byref(h))
+        if (rc == _capi.ERR_UNSUPPORTED and tiled_err_fallback and not (self.options & OPT_TILED_ERR)
+                and b"error sources are served up to" in (L.grape_last_error() or b"")):
+            # refused for its error sources alone (64 < ndim <= 128): once more, on the tiled engine's error path
+            self.options |= OPT_TILED_ERR
             self._bufs.desc.reserved[1] = self.options
             rc = L.grape_plan_create(ctypes.byref(self._bufs.desc), self.device, ctypes.byref(h))
         _capi.check(rc)

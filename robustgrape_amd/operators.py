@@ -224,6 +224,7 @@ OPT_NO_EVAL1 = 16384  # latency-bound calls through the pair-kernel pipeline, no
 OPT_NO_MERGE = 32768  # throughput passes: one walk kernel per sector class instead of merged lanes
 OPT_NO_RANK1 = 65536  # merged gradient walk: the 3x3 / 2x2 matrix state even where M's blocks are of rank one
 OPT_NO_WIDE = 131072  # device-resident calls of rank-one plans: the chunked passes at every count (no wide pass)
+OPT_TILED_ERR = 262144  # 64 < ndim <= 128: the tiled engine takes error sources (F_d2err, F_d2err_dx); ignored below
 
 
 def _reserved(flags: int = 0, options: int = 0, scan_waves: int = 0):
