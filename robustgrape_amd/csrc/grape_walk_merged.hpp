@@ -146,11 +146,13 @@ __device__ __forceinline__ void wide_step_fwd(const cd *Et, const GaugeN<D> (&gn
 }
 // The forward walk in the step frame (ladder charges).  With D_k = diag(p_k^j) (gauge_phases_ladder: e_jm =
 // conj(p^(m-j)), so E_jm = p^j E~_jm p^-m and level j carries charge j), chi_k = D_k^dag psi_k obeys
-//   chi_k = E~ diag(dl^j) chi_{k-1},   dl = p_{k-1} conj(p_k)   (p before the first step: 1, chi = D_0^dag e_c after it)
-// so a step never forms E_k: the re-framing takes dl, dl^2 and D - 1 complex products per sector (20 VALU
+//   chi_k = E~ diag(dl^j) chi_{k-1},   dl = p_{k-1} conj(p_k) = e^{i a (x_{k-1} - x_k)}   (x before the first step: 0)
+// so a step never forms E_k: the re-framing takes dl, dl^2 and D - 1 complex products per sector (16 VALU
 // instructions for one 3-level and one 2-level chain where E_k's formation takes 36), and E~'s entries are the
-// scalar operands of the 9 + 4 complex MACs themselves.  psi_N = D_{N-1} chi_N: one closing re-framing by
-// p_{N-1}.  The same quantity as wide_step_fwd, other roundings.
+// scalar operands of the 9 + 4 complex MACs themselves.  dl is the table phase of the controls' difference: one
+// subtraction where the product of two phases takes four instructions and a carried phase two registers, and its
+// argument is rounded as a x_k is.  psi_N = D_{N-1} chi_N: one closing re-framing by the last step's phase.  The
+// same quantity as wide_step_fwd, other roundings.
 template <int D, int NE, int DP>
 __device__ __forceinline__ void wide_reframe(const cd (&pw)[DP], cd (&chi)[NE][D]) {  // chi_j <- pw[j] chi_j, pw[0] = 1
     static_assert(D <= DP, "powers up to the sector's highest charge");
@@ -255,18 +257,18 @@ __device__ __forceinline__ void wide_fwd_body(const DevProblem &PA, const DevBat
         for (int j = 0; j < 2; ++j) psiB[w][j] = cmake(j == PB.rank1_c[w] ? 1.0 : 0.0, 0.0);
     }
     constexpr bool FRAME = LAD && GRAPE_WIDE_STEP_FRAME;  // (psi holds chi = D_k^dag psi: wide_step_frame)
-    cd pprev = cmake(1.0, 0.0);
+    double xprev = 0.0;  // (the control of the step before: dl from the difference, the first dl conj(p_0))
     auto step = [&](double xk) {
-        const cd p1 = gauge_cis_tab(PA.gauge_a * xk, ctab);
         if constexpr (FRAME) {
             cd pw[DA];
-            ladder_powers<DA>(cmulf(pprev, cconj(p1)), pw);
-            pprev = p1;
+            ladder_powers<DA>(gauge_cis_tab(PA.gauge_a * (xprev - xk), ctab), pw);
+            xprev = xk;
             wide_reframe<DA, 1>(pw, psiA);
             wide_reframe<2, NEB>(pw, psiB);
             wide_step_frame<DA, 1>(PA.gauge_Et, psiA);
             wide_step_frame<2, NEB>(PB.gauge_Et, psiB);
         } else {
+            const cd p1 = gauge_cis_tab(PA.gauge_a * xk, ctab);
             wide_step_fwd<DA, 1, LAD>(PA.gauge_Et, gA, p1, psiA);
             wide_step_fwd<2, NEB, LAD>(PB.gauge_Et, gB, p1, psiB);
         }
@@ -291,7 +293,7 @@ __device__ __forceinline__ void wide_fwd_body(const DevProblem &PA, const DevBat
     }
     if constexpr (FRAME) {  // psi_N = D_{N-1} chi_N: the head and the gradient walk read the lab frame
         cd pw[DA];
-        ladder_powers<DA>(pprev, pw);
+        ladder_powers<DA>(gauge_cis_tab(PA.gauge_a * xprev, ctab), pw);  // (the last step's phase, once per kernel)
         wide_reframe<DA, 1>(pw, psiA);
         wide_reframe<2, NEB>(pw, psiB);
     }
@@ -723,28 +725,24 @@ __device__ __forceinline__ void merged_r1_init(const cd *ca, size_t nbe, const c
         psi[j] = ca[(size_t)(j * D + c) * nbe];
     }
 }
-// One time-reversed gradient step of the wide pass, NSEC sectors over NE propagators: from psi_k and phi_k
-//   psi_{k-1} = E_k^dag psi_k;   v_rj = conj(phi_k,r) (E_k)_rj;   the step's term from v_rj psi_{k-1},j
-//   (grouped by charge difference with the rho weights and 1 / eps, as merged_step_grad_r1);
-//   phi_{k-1},j = conj(sum_r v_rj)
-// Per 3-level sector 36 FMA (psi) + 18 MUL + 18 FMA (v) + 24 FMA (T) + 12 ADD (phi): merged_step_grad_r1's count.
+// One time-reversed gradient step of the wide pass, NSEC sectors over NE propagators, general charges (ladder
+// charges: wide_step_grad_frame below): from psi_k and phi_k
+//   psi_{k-1} = E_k^dag psi_k;   v_rj = conj(phi_k,r) (E_k)_rj;   the step's term sum_{r != j} Re(v_rj psi_{k-1},j f_rj)
+//   over 1 / eps, as merged_step_grad_r1;   phi_{k-1},j = conj(sum_r v_rj)
 // (The diagonal v_jj enter only phi's column sum; as a complex MAC onto the off-diagonal terms they are 10 F64
 // instructions fewer per step and lane, which bought 0.8 % of the gradient walk and nothing that the bench could
 // tell from its run-to-run spread: DESIGN.md 9.)
-// The difference weights come in formed (wide_fd_weights): rh[m] = rho(m) for ladder charges, fw[we] the pair
-// weights of propagator we otherwise.
-template <int D, int NE, int NSEC, bool LAD, int DR>
-__device__ __forceinline__ double wide_step_grad(const cd *Et, const GaugeN<D> (&gn)[NE], cd p1, const cd (&rh)[DR],
+// The difference weights come in formed (wide_fd_weights): fw[we] the pair weights of propagator we.
+template <int D, int NE, int NSEC>
+__device__ __forceinline__ double wide_step_grad(const cd *Et, const GaugeN<D> (&gn)[NE], cd p1,
                                                  const cd (&fw)[NE][kGaugePairs<D>], double inv_eps,
                                                  cd (&psi)[NSEC][D], cd (&phi)[NSEC][D]) {
-    static_assert(D <= DR, "weights up to the sector's highest charge difference");
     constexpr int NSH = NSEC / NE;
     MStore<D, false> E[NE];
 #pragma unroll
     for (int w = 0; w < NE; ++w) {
         cd dph[kGaugePairs<D>];
-        if constexpr (LAD) gauge_phases_ladder<D>(p1, dph);
-        else gauge_phases<D>(p1, gn[w], dph);
+        gauge_phases<D>(p1, gn[w], dph);
         gauge_prop_lds<D, true>(Et + w * D * D, dph, E[w]);
     }
     double tot = 0.0, one = 0.0;
@@ -767,42 +765,14 @@ __device__ __forceinline__ double wide_step_grad(const cd *Et, const GaugeN<D> (
                 for (int j = 0; j < D; ++j) v[r][j] = cmulf(cconj(phi[w][r]), E[we].at(r, j));
             }
             double c = 0.0;
-            if constexpr (LAD) {  // T_m = sum_{r-j=m} v_rj psi_j + conj(sum_{r-j=-m} v_rj psi_j)
-                double tre[D], tim[D];
 #pragma unroll
-                for (int m = 0; m < D; ++m) tre[m] = tim[m] = 0.0;
+            for (int r = 0; r < D; ++r) {  // sum_{r != j} Re(v_rj psi_j f_rj)
 #pragma unroll
-                for (int r = 0; r < D; ++r) {
-#pragma unroll
-                    for (int j = 0; j < D; ++j) {
-                        if (r == j) continue;
-                        const int m = r > j ? r - j : j - r;
-                        tre[m] = fma(v[r][j].re, pm[j].re, tre[m]);
-                        tre[m] = fma(-v[r][j].im, pm[j].im, tre[m]);
-                        if (r > j) {
-                            tim[m] = fma(v[r][j].re, pm[j].im, tim[m]);
-                            tim[m] = fma(v[r][j].im, pm[j].re, tim[m]);
-                        } else {
-                            tim[m] = fma(-v[r][j].re, pm[j].im, tim[m]);
-                            tim[m] = fma(-v[r][j].im, pm[j].re, tim[m]);
-                        }
-                    }
-                }
-#pragma unroll
-                for (int m = 1; m < D; ++m) {
-                    c = fma(rh[m].re, tre[m], c);
-                    c = fma(-rh[m].im, tim[m], c);
-                }
-            } else {  // sum_{r != j} Re(v_rj psi_j f_rj)
-#pragma unroll
-                for (int r = 0; r < D; ++r) {
-#pragma unroll
-                    for (int j = 0; j < D; ++j) {
-                        if (r == j) continue;
-                        const cd z = cmulf(v[r][j], pm[j]), g = gauge_fd_weight<D>(fw[we], r, j);
-                        c = fma(z.re, g.re, c);
-                        c = fma(-z.im, g.im, c);
-                    }
+                for (int j = 0; j < D; ++j) {
+                    if (r == j) continue;
+                    const cd z = cmulf(v[r][j], pm[j]), g = gauge_fd_weight<D>(fw[we], r, j);
+                    c = fma(z.re, g.re, c);
+                    c = fma(-z.im, g.im, c);
                 }
             }
             const double sv = c * inv_eps;
@@ -815,6 +785,81 @@ __device__ __forceinline__ double wide_step_grad(const cd *Et, const GaugeN<D> (
                 for (int r = 1; r < D; ++r) s = cadd(s, v[r][j]);
                 phi[w][j] = cconj(s);
                 psi[w][j] = pm[j];
+            }
+        }
+    }
+    return NSEC > 1 ? tot : one;
+}
+// The same step in the step frame (ladder charges).  With chi = D_k^dag psi_k and eta = D_k^dag phi_k,
+//   chi' = D_k^dag psi_{k-1} = E~^dag chi,   eta' = D_k^dag phi_{k-1} = E~^dag eta,
+//   conj(phi_k,r) (E_k)_rj psi_{k-1},j = conj(eta_r) E~_rj chi'_j   entry by entry (the phases p_k^r p_k^-j cancel),
+// so the step is wide_step_grad's with E~ for E_k and (eta, chi') for (phi, psi): E_k is never formed (36 VALU
+// instructions and 52 registers for one 3-level and one 2-level propagator), and E~'s entries are the scalar
+// operands of the products themselves (per-step scalar loads, as wide_step_frame).  The caller re-frames chi and
+// eta from step k + 1's frame before the step (wide_reframe by dl = e^{i a (x_{k+1} - x_k)}).  The same quantity as
+// wide_step_grad, other roundings.
+template <int D, int NE, int NSEC, int DR>
+__device__ __forceinline__ double wide_step_grad_frame(const cd *Et, const cd (&rh)[DR], double inv_eps,
+                                                       cd (&chi)[NSEC][D], cd (&eta)[NSEC][D]) {
+    static_assert(D <= DR, "weights up to the sector's highest charge difference");
+    constexpr int NSH = NSEC / NE;
+    double tot = 0.0, one = 0.0;
+#pragma unroll
+    for (int we = 0; we < NE; ++we) {
+        cptr<cd> g = as_constant(Et + we * D * D);
+        asm volatile("" : "+s"(g));
+#pragma unroll
+        for (int t = 0; t < NSH; ++t) {
+            const int w = we * NSH + t;
+            cd pm[D], v[D][D];
+#pragma unroll
+            for (int j = 0; j < D; ++j) {  // chi' = E~^dag chi
+                cd s = czero();
+#pragma unroll
+                for (int r = 0; r < D; ++r) cmac(s, cconj(cload(g, r * D + j)), chi[w][r]);
+                pm[j] = s;
+            }
+#pragma unroll
+            for (int r = 0; r < D; ++r) {
+#pragma unroll
+                for (int j = 0; j < D; ++j) v[r][j] = cmulf(cconj(eta[w][r]), cload(g, r * D + j));
+            }
+            double tre[D], tim[D];  // T_m = sum_{r-j=m} v_rj chi'_j + conj(sum_{r-j=-m} v_rj chi'_j)
+#pragma unroll
+            for (int m = 0; m < D; ++m) tre[m] = tim[m] = 0.0;
+#pragma unroll
+            for (int r = 0; r < D; ++r) {
+#pragma unroll
+                for (int j = 0; j < D; ++j) {
+                    if (r == j) continue;
+                    const int m = r > j ? r - j : j - r;
+                    tre[m] = fma(v[r][j].re, pm[j].re, tre[m]);
+                    tre[m] = fma(-v[r][j].im, pm[j].im, tre[m]);
+                    if (r > j) {
+                        tim[m] = fma(v[r][j].re, pm[j].im, tim[m]);
+                        tim[m] = fma(v[r][j].im, pm[j].re, tim[m]);
+                    } else {
+                        tim[m] = fma(-v[r][j].re, pm[j].im, tim[m]);
+                        tim[m] = fma(-v[r][j].im, pm[j].re, tim[m]);
+                    }
+                }
+            }
+            double c = 0.0;
+#pragma unroll
+            for (int m = 1; m < D; ++m) {
+                c = fma(rh[m].re, tre[m], c);
+                c = fma(-rh[m].im, tim[m], c);
+            }
+            const double sv = c * inv_eps;
+            tot += sv;
+            one = sv;
+#pragma unroll
+            for (int j = 0; j < D; ++j) {  // eta' = E~^dag eta = conj of the column sums of v
+                cd s = v[0][j];
+#pragma unroll
+                for (int r = 1; r < D; ++r) s = cadd(s, v[r][j]);
+                eta[w][j] = cconj(s);
+                chi[w][j] = pm[j];
             }
         }
     }
@@ -945,14 +990,34 @@ __device__ __forceinline__ void wide_grad_body(const DevProblem &PA, const DevBa
     for (int w = 0; w < NEB; ++w) gB[w] = gauge_charges<2>(PB, w);
     WideFd<DA, NEB, LAD> fd;
     wide_fd_base<DA, NEB, LAD>(PA.gauge_a, PA.eps, gA, gB, fd);
+    // Ladder charges: the walk runs in the step frame (wide_step_grad_frame).  psi and phi hold chi = D^dag psi and
+    // eta = D^dag phi in the frame of the step walked last -- the lab frame before the first one, as psi_N is stored
+    // and phi_N is formed: x "of the step before" starts at 0 -- and a step re-frames both by
+    // dl = e^{i a (xlast - x_k)} before its products.  xlast is the lane's own register: the tile slot it came from
+    // holds the step's F_dx value by then, and the tile itself is replaced at a seam.
+    double xlast = 0.0;
     auto step = [&](double xk) {  // one step of both classes: the F_dx value, in the plan's class order
         const double xe = xk + PA.eps;
-        const cd p1 = gauge_cis_tab(PA.gauge_a * xk, ctab);
         cd rh[DA], fwA[1][kGaugePairs<DA>], fwB[NEB][1];
-        wide_fd_weights<DA, NEB, LAD>(fd, PA.gauge_a, xe - xk, gA, gB, rh, fwA, fwB);  // (xe - xk: exact)
-        const double sa = wide_step_grad<DA, 1, 1, LAD>(PA.gauge_Et, gA, p1, rh, fwA, PA.inv_eps, psiA, phiA);
-        const double sb = wide_step_grad<2, NEB, NXB, LAD>(PB.gauge_Et, gB, p1, rh, fwB, PB.inv_eps, psiB, phiB);
-        return sa + sb;  // (the classes' parts in either order: see k_walk_grad_m's step)
+        if constexpr (LAD) {
+            cd pw[DA];
+            ladder_powers<DA>(gauge_cis_tab(PA.gauge_a * (xlast - xk), ctab), pw);
+            xlast = xk;
+            wide_fd_weights<DA, NEB, LAD>(fd, PA.gauge_a, xe - xk, gA, gB, rh, fwA, fwB);  // (xe - xk: exact)
+            wide_reframe<DA, 1>(pw, psiA);
+            wide_reframe<DA, 1>(pw, phiA);
+            wide_reframe<2, NXB>(pw, psiB);
+            wide_reframe<2, NXB>(pw, phiB);
+            const double sa = wide_step_grad_frame<DA, 1, 1>(PA.gauge_Et, rh, PA.inv_eps, psiA, phiA);
+            const double sb = wide_step_grad_frame<2, NEB, NXB>(PB.gauge_Et, rh, PB.inv_eps, psiB, phiB);
+            return sa + sb;
+        } else {
+            const cd p1 = gauge_cis_tab(PA.gauge_a * xk, ctab);
+            wide_fd_weights<DA, NEB, LAD>(fd, PA.gauge_a, xe - xk, gA, gB, rh, fwA, fwB);  // (xe - xk: exact)
+            const double sa = wide_step_grad<DA, 1, 1>(PA.gauge_Et, gA, p1, fwA, PA.inv_eps, psiA, phiA);
+            const double sb = wide_step_grad<2, NEB, NXB>(PB.gauge_Et, gB, p1, fwB, PB.inv_eps, psiB, phiB);
+            return sa + sb;  // (the classes' parts in either order: see k_walk_grad_m's step)
+        }
     };
     // The tiles and the steps of a tile in descending order.  One workgroup tile serves both ways: it arrives
     // holding the tile's controls (wide_load_x), each lane replaces x_k in its row by the step's F_dx value, and the
