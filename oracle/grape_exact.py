@@ -22,7 +22,8 @@ included: the quantity
 the reference means to return, against which the noise of the oracle, the C++ port and the device
 paths can each be read off (scripts/probes/fd_exact_probe.py, tests/test_gpu_gauge.py).
 
-Scope: no error sources (F, F_dx, F_dx_add), H0 free of x_add (the target part of F_dx_add only).
+Scope: no error sources (F, F_dx, F_dx_add), H0 free of x_add (the target part of F_dx_add only);
+fidelity_and_gradient_xadd takes an H0 that reads x_add (F and F_dx, with the propagators' part of F_dx_add).
 Every step's H0 (and H0 + Herror in the evaluators with error sources) must be Hermitian to rounding: the
 chain's inverse is taken as C_k^dagger, so anything else raises ValueError (_require_hermitian).
 """
@@ -178,6 +179,67 @@ def fidelity_and_gradient(fp, x, nparam=1):
         Fdx[nt * nparam + q] = float(np.real(tr_mod(P @ ct(U0d) @ U @ P @ ct(U) @ U0
                                                     + P @ ct(U0) @ U @ P @ ct(U) @ U0d))
                                      + 2 * np.real(tau_c * tr_mod(P @ ct(U0d) @ U))) / DD
+    return float(F), Fdx
+
+
+def fidelity_and_gradient_xadd(fp, x, nparam=1):
+    """(F, F_dx_tot) like fidelity_and_gradient, for an H0 that may read x_add: the additional parameters then
+    also move every step's propagator, U_dx_add[q] = U sum_k C_k^dag ((exp(-i dt H0(k, x_k, x_add + eps e_q))
+    - E_k) / eps) C_{k-1} (UnitaryCalculations.jl:57-64, 119-121), and F_dx_add[q] holds that term next to the
+    target's difference (FidelityCalculations.jl:67-76).  Error sources are left out: F and F_dx do not depend on
+    them.  With an H0 free of x_add the differences vanish exactly and the result is fidelity_and_gradient's."""
+    up = fp.unitary_problem
+    nt, d, na = up.ntimes, up.ndim, up.nb_additional_param
+    eps = up.eps
+    dt = up.t0 / nt
+    x = np.asarray(x, dtype=np.float64)
+    xm = x[:len(x) - na].reshape(nt, nparam)
+    xa = x[len(x) - na:].copy()
+    cdt = LD(-1j * dt)
+    ct = lambda A: A.conj().T  # noqa: E731
+    C = np.eye(d, dtype=LD)
+    Vdx = np.zeros((nparam, nt, d, d), dtype=LD)
+    Vadd = np.zeros((na, d, d), dtype=LD)
+    for k in range(nt):
+        H0k = _h0_ld(up.H0, k + 1, xm[k], xa)
+        _require_hermitian(H0k, "H0", k + 1)
+        E = exp_ld(cdt * H0k)
+        Cold, C = C, E @ C
+        Ci = ct(C)
+        for p in range(nparam):
+            xp = xm[k].copy()
+            xp[p] = xp[p] + eps
+            Vdx[p, k] = Ci @ ((exp_ld(cdt * _h0_ld(up.H0, k + 1, xp, xa)) - E) / LD(eps)) @ Cold
+        for q in range(na):
+            xq = xa.copy()
+            xq[q] = xq[q] + eps
+            Vadd[q] = Vadd[q] + Ci @ ((exp_ld(cdt * _h0_ld(up.H0, k + 1, xm[k], xq)) - E) / LD(eps)) @ Cold
+    U = C
+    P0 = np.asarray(fp.projector, dtype=np.complex128)
+    P = P0.copy()
+    P[P != 0] = 1
+    Dn = float(np.real(np.trace(P0)))
+    P0, P = P0.astype(LD), P.astype(LD)
+    DD = Dn * (Dn + 1)
+    tr_mod = lambda A: np.trace(P0 @ A)  # noqa: E731
+    U0 = _target_ld(fp.target_unitary, xa)
+    F = (np.real(tr_mod(P @ ct(U0) @ U @ P @ ct(U) @ U0)) + abs(tr_mod(P @ ct(U0) @ U)) ** 2) / DD
+    tau_c = np.conj(tr_mod(P @ ct(U0) @ U))
+
+    def lin(Ud):  # the terms of :58-63 linear in a derivative Ud of U
+        return (np.real(tr_mod(P @ ct(U0) @ Ud @ P @ ct(U) @ U0 + P @ ct(U0) @ U @ P @ ct(Ud) @ U0))
+                + 2 * np.real(tau_c * tr_mod(P @ ct(U0) @ Ud)))
+    Fdx = np.zeros(nt * nparam + na)
+    for k in range(nt):
+        for p in range(nparam):
+            Fdx[k * nparam + p] = float(lin(U @ Vdx[p, k]) / DD)
+    for q in range(na):
+        xq = xa.copy()
+        xq[q] = xq[q] + eps
+        U0d = (_target_ld(fp.target_unitary, xq) - U0) / LD(eps)
+        tgt = (np.real(tr_mod(P @ ct(U0d) @ U @ P @ ct(U) @ U0 + P @ ct(U0) @ U @ P @ ct(U) @ U0d))
+               + 2 * np.real(tau_c * tr_mod(P @ ct(U0d) @ U)))
+        Fdx[nt * nparam + q] = float((lin(U @ Vadd[q]) + tgt) / DD)
     return float(F), Fdx
 
 
