@@ -1,7 +1,8 @@
 // grape_dense.hip -- the dense engine's kernels (13 <= d <= 64, padded to 64):
 //
 //   k_dexp    one workgroup per (eval b, step k): A_k = -i dt H(x_b,k) from the
-//             operator basis, E_k = exp(A_k) on MFMA.      UnitaryCalculations.jl:45
+//             operator basis, E_k = exp(A_k) on MFMA (k_dexp<true>: the pivoted solve of a
+//             general A; k_dexp_raw: A given as an image).  UnitaryCalculations.jl:45
 //   k_dscan   one workgroup per (b, chunk c): chunk-local prefix products
 //             Q_k = E_k Q_{k-1} (Q = E at a chunk start).  UnitaryCalculations.jl:46-47
 //   k_dcarry  one workgroup per b: carries Carry_c = Q_{end(c-1)} Carry_{c-1},
@@ -12,6 +13,8 @@
 //             then for every control p the eps-variant exponential E' and
 //             F_dx[p,k] = Re sum(Z_k o (E' - E_k)/eps).   UnitaryCalculations.jl:48-52,
 //                                                        FidelityCalculations.jl:56-65
+//   k_dadd    one workgroup per (row, q): the steps' x_add terms summed onto the target's part
+//             of F_dx_add (rows b) and of F_d2err_dx_add (rows (b, e))
 // With error sources (the algebra of grape_errpath.hpp on 64 x 64 images):
 //   k_dexp       every propagator variant of every step (nominal, eps / eps2 controls,
 //                error eps / eps2, mixed)                 UnitaryCalculations.jl:45-83
@@ -34,21 +37,6 @@ namespace grape_dense {
 namespace {
 
 constexpr grape::Pert kNoPert = {-1, 0, 0.0};
-
-// A = -i dt (sum_t c_t OP_t) for step k of eval b, one variable perturbed
-__device__ __forceinline__ void build_generator(const DenseProblem &DP, const double *xb, int k, const grape::Pert &pp,
-                                                HM &A, const Lane &ln) {
-    const grape::DevProblem &P = DP.P;
-    const double *xk = xb + (size_t)k * P.np;
-    const double *xadd = xb + (size_t)P.np * P.Nt;
-    hm_zero(A);
-    for (int t = 0; t < P.n_h0; ++t) {
-        const Term tm = P.h0[t];
-        const cd c = grape::term_coef(tm, k + 1, xk, xadd, pp);
-        const cd g = grape::cmake(P.dt * c.im, -(P.dt * c.re));  // -i dt c
-        hm_cmac_img(A, g, DP.opimg + (size_t)tm.op * IMG, ln);
-    }
-}
 
 // A = -i dt (H0 + errval Herror_e) of propagator variant v (grape::VSpec) for step k of eval b
 // (UnitaryCalculations.jl:45-90: the perturbed variable in both, H0's terms first)
@@ -111,10 +99,82 @@ __device__ __forceinline__ void build_target(const DenseProblem &DP, const doubl
     }
 }
 
+// (U0(x_add + eps e_q) - U0) / eps
+__device__ __forceinline__ void build_target_diff(const DenseProblem &DP, const double *xb, int q, const HM &U0, HM &D,
+                                                  const Lane &ln) {
+    grape::Pert pq;
+    pq.var = grape::VAR_XADD;
+    pq.index = q;
+    pq.delta = DP.P.eps;
+    build_target(DP, xb, pq, D, ln);
+    hm_sub(D, U0);
+    hm_scale(D, DP.P.inv_eps);
+}
+
+// M <- W M: row i scaled by W_i
+__device__ __forceinline__ void hm_wrows(const DenseProblem &DP, HM &M, const Lane &ln) {
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const double wr = DP.W[ln.row(i, r)];
+            M.re[i][r] *= wr;
+            M.im[i][r] *= wr;
+        }
+}
+
+// the workgroup sums of a head: s = sum_ij W_i P_j Re(conj(B_ij) A_ij) and tr = tr(W A).  A = B = K: F's own sums
+// (FidelityCalculations.jl:47-54); A a derivative of K: a target row of F_dx_add (:67-76); Ke for K: the error head
+struct HeadSums {
+    double s, tr_re, tr_im;
+};
+__device__ __forceinline__ HeadSums head_sums(const DenseProblem &DP, const HM &A, const HM &Bm, double *lds,
+                                              const Lane &ln) {
+    const int col = ln.col();
+    const double pcol = DP.W[col] != 0.0 ? 1.0 : 0.0;
+    double part = 0.0, tre = 0.0, tim = 0.0;
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const int row = ln.row(i, r);
+            const double wr = DP.W[row];
+            part += wr * (pcol * (A.re[i][r] * Bm.re[i][r] + A.im[i][r] * Bm.im[i][r]));
+            if (row == col) {
+                tre += wr * A.re[i][r];
+                tim += wr * A.im[i][r];
+            }
+        }
+    HeadSums h;
+    h.s = wg_sum(part, lds, ln);
+    h.tr_re = wg_sum(tre, lds, ln);
+    h.tr_im = wg_sum(tim, lds, ln);
+    return h;
+}
+
+// out = Carry Y Carry^dag: Carry in S0, Y the image at img, X scratch.  WAIT: the workgroup's last product may
+// still be reading S1
+template <bool WAIT>
+__device__ __forceinline__ void conj_by_carry(const double *img, SM S0, SM S1, HM &X, HM &out, const Lane &ln) {
+    img_load(img, X, ln);
+    if (WAIT) __syncthreads();
+    sm_store(S1, X, ln);
+    __syncthreads();
+    hm_zero(X);
+    mm<false, false, false, false>(S0, S1, X, ln);  // Carry Y
+    __syncthreads();
+    sm_store(S1, X, ln);
+    __syncthreads();
+    hm_zero(out);
+    mm<false, false, true, true>(S1, S0, out, ln);  // (Carry Y) Carry^dag
+}
+
 __device__ __forceinline__ void note_m(int *mstats, int m) {
     if (mstats && threadIdx.x == 0) atomicAdd(mstats + m_index(m), 1);
 }
 
+// PIV: wg_expm<true>, the pivoted Pade solve of a general generator (grape_dense.hpp)
+template <bool PIV>
 __global__ __launch_bounds__(NTHREADS, 1) void k_dexp(DenseProblem DP, DenseBatch B) {
     extern __shared__ double lds[];
     const Lane ln = make_lane();
@@ -125,49 +185,20 @@ __global__ __launch_bounds__(NTHREADS, 1) void k_dexp(DenseProblem DP, DenseBatc
     const double *xb = B.x + (size_t)b * P.nx;
     bool singular = false;
     const grape::VSpec vs = P.vs[v];
-    const int m = wg_expm([&](HM &A) { build_variant(DP, xb, k, vs, A, ln); }, X, lds, ln, singular);
+    const int m = wg_expm<PIV>([&](HM &A) { build_variant(DP, xb, k, vs, A, ln); }, X, lds, ln, singular);
     img_store(B.E + (size_t)item * IMG, X, ln);
     if (singular) atomicOr(B.status, 1);
     note_m(B.mstats, m);
 }
 
+template <bool PIV>
 __global__ __launch_bounds__(NTHREADS, 1) void k_dexp_raw(const double *Ain, double *Eout, int *status, int *mstats) {
     extern __shared__ double lds[];
     const Lane ln = make_lane();
     HM X;
     const double *src = Ain + (size_t)blockIdx.x * IMG;
     bool singular = false;
-    const int m = wg_expm([&](HM &A) { img_load(src, A, ln); }, X, lds, ln, singular);
-    img_store(Eout + (size_t)blockIdx.x * IMG, X, ln);
-    if (singular) atomicOr(status, 1);
-    note_m(mstats, m);
-}
-
-// k_dexp / k_dexp_raw for a general generator: wg_expm<true> (pivoted Pade solve, grape_dense.hpp)
-__global__ __launch_bounds__(NTHREADS, 1) void k_dexp_piv(DenseProblem DP, DenseBatch B) {
-    extern __shared__ double lds[];
-    const Lane ln = make_lane();
-    const grape::DevProblem &P = DP.P;
-    const long item = blockIdx.x;  // (b, k, v), v fastest; E[b][k][v]
-    const int v = (int)(item % P.nv), k = (int)((item / P.nv) % P.Nt), b = (int)(item / ((long)P.nv * P.Nt));
-    HM X;
-    const double *xb = B.x + (size_t)b * P.nx;
-    bool singular = false;
-    const grape::VSpec vs = P.vs[v];
-    const int m = wg_expm<true>([&](HM &A) { build_variant(DP, xb, k, vs, A, ln); }, X, lds, ln, singular);
-    img_store(B.E + (size_t)item * IMG, X, ln);
-    if (singular) atomicOr(B.status, 1);
-    note_m(B.mstats, m);
-}
-
-__global__ __launch_bounds__(NTHREADS, 1) void k_dexp_raw_piv(const double *Ain, double *Eout, int *status,
-                                                               int *mstats) {
-    extern __shared__ double lds[];
-    const Lane ln = make_lane();
-    HM X;
-    const double *src = Ain + (size_t)blockIdx.x * IMG;
-    bool singular = false;
-    const int m = wg_expm<true>([&](HM &A) { img_load(src, A, ln); }, X, lds, ln, singular);
+    const int m = wg_expm<PIV>([&](HM &A) { img_load(src, A, ln); }, X, lds, ln, singular);
     img_store(Eout + (size_t)blockIdx.x * IMG, X, ln);
     if (singular) atomicOr(status, 1);
     note_m(mstats, m);
@@ -232,36 +263,12 @@ __global__ __launch_bounds__(NTHREADS, 1) void k_dcarry(DenseProblem DP, DenseBa
     __syncthreads();
     hm_zero(K);
     mm<true, true, false, false>(S0, S1, K, ln);
-    const int col = ln.col();
-    const double pcol = DP.W[col] != 0.0 ? 1.0 : 0.0;
-    double part = 0.0, tre = 0.0, tim = 0.0;
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const int row = ln.row(i, r);
-            const double wr = DP.W[row];
-            const double kr = K.re[i][r], ki = K.im[i][r];
-            part += wr * (pcol * (kr * kr + ki * ki));
-            if (row == col) {
-                tre += wr * kr;
-                tim += wr * ki;
-            }
-        }
-    const double sum_part = wg_sum(part, lds, ln);
-    const double tau_re = wg_sum(tre, lds, ln);
-    const double tau_im = wg_sum(tim, lds, ln);
-    const double Fv = (sum_part + tau_re * tau_re + tau_im * tau_im) / P.DD;
+    const HeadSums hk = head_sums(DP, K, K, lds, ln);
+    const double tau_re = hk.tr_re, tau_im = hk.tr_im;
+    const double Fv = (hk.s + tau_re * tau_re + tau_im * tau_im) / P.DD;
     // M = (2/DD) (P K^dag W K + conj(tau) W K) with T = K^dag (W K)
     HM WK = K;
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const double wr = DP.W[ln.row(i, r)];
-            WK.re[i][r] *= wr;
-            WK.im[i][r] *= wr;
-        }
+    hm_wrows(DP, WK, ln);
     __syncthreads();
     sm_store(S0, K, ln);
     sm_store(S1, WK, ln);
@@ -284,42 +291,18 @@ __global__ __launch_bounds__(NTHREADS, 1) void k_dcarry(DenseProblem DP, DenseBa
     img_store(B.M + (size_t)b * IMG, Mm, ln);
     // target derivative part of F_dx_add (FidelityCalculations.jl:34-40, 67-76)
     for (int q = 0; q < P.na; ++q) {
-        grape::Pert pq;
-        pq.var = grape::VAR_XADD;
-        pq.index = q;
-        pq.delta = P.eps;
         HM U0e, Kd;
-        build_target(DP, xb, pq, U0e, ln);
-#pragma unroll
-        for (int i = 0; i < 2; ++i) {
-            U0e.re[i] = (U0e.re[i] - U0.re[i]) * P.inv_eps;
-            U0e.im[i] = (U0e.im[i] - U0.im[i]) * P.inv_eps;
-        }
+        build_target_diff(DP, xb, q, U0, U0e, ln);
         __syncthreads();
         sm_store(S0, U0e, ln);
         sm_store(S1, U, ln);
         __syncthreads();
         hm_zero(Kd);
         mm<true, true, false, false>(S0, S1, Kd, ln);
-        double pr = 0.0, dre = 0.0, dim = 0.0;
-#pragma unroll
-        for (int i = 0; i < 2; ++i)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int row = ln.row(i, r);
-                const double wr = DP.W[row];
-                pr += wr * (pcol * (Kd.re[i][r] * K.re[i][r] + Kd.im[i][r] * K.im[i][r]));
-                if (row == col) {
-                    dre += wr * Kd.re[i][r];
-                    dim += wr * Kd.im[i][r];
-                }
-            }
-        const double s1 = wg_sum(pr, lds, ln);
-        const double tr_re = wg_sum(dre, lds, ln);
-        const double tr_im = wg_sum(dim, lds, ln);
+        const HeadSums hd = head_sums(DP, Kd, K, lds, ln);
         if (threadIdx.x == 0)
             B.Fdx[(size_t)b * P.nx + (size_t)P.np * P.Nt + q] =
-                (2.0 * s1 + 2.0 * (tau_re * tr_re + tau_im * tr_im)) / P.DD;
+                (2.0 * hd.s + 2.0 * (tau_re * hd.tr_re + tau_im * hd.tr_im)) / P.DD;
     }
     if (threadIdx.x == 0) B.F[b] = Fv;
 }
@@ -330,20 +313,11 @@ __global__ __launch_bounds__(NTHREADS, 1) void k_dmc(DenseProblem DP, DenseBatch
     const Lane ln = make_lane();
     const int b = blockIdx.x / DP.Nc, c = blockIdx.x % DP.Nc;
     SM S0 = sm_at(lds, LDS_R0), S1 = sm_at(lds, LDS_R1);
-    HM X, T;
+    HM X, Mc;
     img_load(B.Carry + ((size_t)b * DP.Nc + c) * IMG, X, ln);
     sm_store(S0, X, ln);
-    img_load(B.M + (size_t)b * IMG, X, ln);
-    sm_store(S1, X, ln);
-    __syncthreads();
-    hm_zero(T);
-    mm<false, false, false, false>(S0, S1, T, ln);  // Carry M
-    __syncthreads();
-    sm_store(S1, T, ln);
-    __syncthreads();
-    hm_zero(X);
-    mm<false, false, true, true>(S1, S0, X, ln);  // (Carry M) Carry^dagger
-    img_store(B.Mc + ((size_t)b * DP.Nc + c) * IMG, X, ln);
+    conj_by_carry<false>(B.M + (size_t)b * IMG, S0, S1, X, Mc, ln);
+    img_store(B.Mc + ((size_t)b * DP.Nc + c) * IMG, Mc, ln);
 }
 
 // F_dx[p, k] for every control p of step k, and (H0 reading x_add, DP.nva > 0) step k's term of
@@ -387,7 +361,7 @@ __global__ __launch_bounds__(NTHREADS, 1) void k_dgrad(DenseProblem DP, DenseBat
         pp.delta = P.eps;
         HM A, X;
         bool singular = false;
-        wg_expm([&](HM &G) { build_generator(DP, xb, k, pp, G, ln); }, X, lds, ln, singular);
+        wg_expm([&](HM &G) { build_variant(DP, xb, k, grape::VSpec{pp, -1, 0.0}, G, ln); }, X, lds, ln, singular);
         if (singular) atomicOr(B.status, 1);
         img_load(B.E + (qbase + k) * IMG, A, ln);
         img_load(zimg, Z, ln);  // written by this same lane above
@@ -408,38 +382,22 @@ __global__ __launch_bounds__(NTHREADS, 1) void k_dgrad(DenseProblem DP, DenseBat
     }
 }
 
-// F_dx_add[q] += sum_k Fadd[k][q] (after k_dcarry wrote the target's part), one workgroup per (b, q),
-// fixed summation order
-__global__ __launch_bounds__(256) void k_dadd(DenseProblem DP, DenseBatch B) {
+// dst[row][np Nt + q] += sum_k src[row][k][q], one workgroup per (row, q), fixed summation order.  Rows b: Fadd into
+// F_dx_add after k_dcarry wrote the target's part; rows (b, e): Fd2add into F_d2err_dx_add after k_derr_scan /
+// the error head wrote theirs
+__global__ __launch_bounds__(256) void k_dadd(DenseProblem DP, const double *src, double *dst) {
     const grape::DevProblem &P = DP.P;
-    const int b = blockIdx.x / DP.nva, q = blockIdx.x % DP.nva;
+    const int row = blockIdx.x / DP.nva, q = blockIdx.x % DP.nva;
     __shared__ double red[256];
     double s = 0.0;
-    for (int k = threadIdx.x; k < P.Nt; k += 256) s += B.Fadd[((size_t)b * P.Nt + k) * DP.nva + q];
+    for (int k = threadIdx.x; k < P.Nt; k += 256) s += src[((size_t)row * P.Nt + k) * DP.nva + q];
     red[threadIdx.x] = s;
     __syncthreads();
     for (int w = 128; w > 0; w >>= 1) {
         if ((int)threadIdx.x < w) red[threadIdx.x] += red[threadIdx.x + w];
         __syncthreads();
     }
-    if (threadIdx.x == 0) B.Fdx[(size_t)b * P.nx + (size_t)P.np * P.Nt + q] += red[0];
-}
-
-// F_d2err_dx_add[q, e] += sum_k Fd2add[e][k][q] (after k_derr_scan / the error head wrote the target's
-// part), one workgroup per (b, e, q), fixed summation order
-__global__ __launch_bounds__(256) void k_dadd_err(DenseProblem DP, DenseBatch B) {
-    const grape::DevProblem &P = DP.P;
-    const int q = blockIdx.x % DP.nva, be = blockIdx.x / DP.nva;
-    __shared__ double red[256];
-    double s = 0.0;
-    for (int k = threadIdx.x; k < P.Nt; k += 256) s += B.Fd2add[((size_t)be * P.Nt + k) * DP.nva + q];
-    red[threadIdx.x] = s;
-    __syncthreads();
-    for (int w = 128; w > 0; w >>= 1) {
-        if ((int)threadIdx.x < w) red[threadIdx.x] += red[threadIdx.x + w];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) B.Fd2dx[(size_t)be * P.nx + (size_t)P.np * P.Nt + q] += red[0];
+    if (threadIdx.x == 0) dst[(size_t)row * P.nx + (size_t)P.np * P.Nt + q] += red[0];
 }
 
 // ---------------------------------------------------------------------------
@@ -567,57 +525,30 @@ __global__ __launch_bounds__(NTHREADS, 1) void k_derr_scan(DenseProblem DP, Dens
     __syncthreads();
     hm_zero(Ke);
     mm<true, true, false, false>(S0, S1, Ke, ln);  // Ke = U0^dag Ue
-    const int col = ln.col();
-    const double wcol = DP.W[col], pcol = wcol != 0.0 ? 1.0 : 0.0;
-    double a1 = 0.0, a2 = 0.0, tre = 0.0, tim = 0.0;
+    const HeadSums he = head_sums(DP, Ke, Ke, lds, ln);
+    const double s_a1 = he.s, te_re = he.tr_re, te_im = he.tr_im, wcol = DP.W[ln.col()];
+    double a2 = 0.0;
 #pragma unroll
     for (int i = 0; i < 2; ++i)
 #pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const int row = ln.row(i, r);
-            const double wr = DP.W[row];
-            a1 += wr * (pcol * (Ke.re[i][r] * Ke.re[i][r] + Ke.im[i][r] * Ke.im[i][r]));
+        for (int r = 0; r < 4; ++r)
             a2 += wcol * (Ue.re[i][r] * Ue.re[i][r] + Ue.im[i][r] * Ue.im[i][r]);  // W_j (Ue^dag Ue)_jj
-            if (row == col) {
-                tre += wr * Ke.re[i][r];
-                tim += wr * Ke.im[i][r];
-            }
-        }
-    const double s_a1 = wg_sum(a1, lds, ln), s_a2 = wg_sum(a2, lds, ln);
-    const double te_re = wg_sum(tre, lds, ln), te_im = wg_sum(tim, lds, ln);
+    const double s_a2 = wg_sum(a2, lds, ln);
     // F_d2err = 2[sum W_i P_j |Ke_ij|^2 - (1+D) sum W (Ue^dag Ue)_ii + |te|^2] / (D(D+1))   (:79-83)
     const double fd2 = 2.0 * (s_a1 - (1.0 + P.Dtr) * s_a2 + te_re * te_re + te_im * te_im) / P.DD;
     // target part of F_d2err_dx_add (FidelityCalculations.jl:100-112, the U0_dx_add terms)
     for (int q = 0; q < P.na; ++q) {
-        grape::Pert pq;
-        pq.var = grape::VAR_XADD;
-        pq.index = q;
-        pq.delta = P.eps;
         HM U0e;
-        build_target(DP, xb, pq, U0e, ln);
-        hm_sub(U0e, U0);
-        hm_scale(U0e, P.inv_eps);
+        build_target_diff(DP, xb, q, U0, U0e, ln);
         __syncthreads();
         sm_store(S0, U0e, ln);
         __syncthreads();
         hm_zero(T);
         mm<true, true, false, false>(S0, S1, T, ln);  // Kde = U0d^dag Ue (S1 still holds Ue)
-        double pr = 0.0, dre = 0.0, dim = 0.0;
-#pragma unroll
-        for (int i = 0; i < 2; ++i)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int row = ln.row(i, r);
-                const double wr = DP.W[row];
-                pr += wr * (pcol * (T.re[i][r] * Ke.re[i][r] + T.im[i][r] * Ke.im[i][r]));
-                if (row == col) {
-                    dre += wr * T.re[i][r];
-                    dim += wr * T.im[i][r];
-                }
-            }
-        const double s1 = wg_sum(pr, lds, ln), tr_re = wg_sum(dre, lds, ln), tr_im = wg_sum(dim, lds, ln);
+        const HeadSums hd = head_sums(DP, T, Ke, lds, ln);
         if (threadIdx.x == 0)
-            B.Fd2dx[be * P.nx + (size_t)P.np * P.Nt + q] = 2.0 * (2.0 * s1 + 2.0 * (te_re * tr_re + te_im * tr_im)) / P.DD;
+            B.Fd2dx[be * P.nx + (size_t)P.np * P.Nt + q] =
+                2.0 * (2.0 * hd.s + 2.0 * (te_re * hd.tr_re + te_im * hd.tr_im)) / P.DD;
     }
     if (threadIdx.x == 0) B.Fd2[be] = fd2;
     // M_e = (4/DD) [P Ke^dag W K + conj(te) W K - (1+D) W Ue^dag U],  K = U0^dag U
@@ -634,14 +565,7 @@ __global__ __launch_bounds__(NTHREADS, 1) void k_derr_scan(DenseProblem DP, Dens
     hm_zero(T);
     mm<true, true, false, false>(S0, S1, T, ln);  // Ue^dag U
     HM WK = K;
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const double wr = DP.W[ln.row(i, r)];
-            WK.re[i][r] *= wr;
-            WK.im[i][r] *= wr;
-        }
+    hm_wrows(DP, WK, ln);
     __syncthreads();
     sm_store(S0, Ke, ln);
     sm_store(S1, WK, ln);
@@ -677,23 +601,10 @@ __global__ __launch_bounds__(NTHREADS, 1) void k_dmce(DenseProblem DP, DenseBatc
     HM X, Mp, Tc, Tt;
     img_load(B.Carry + ((size_t)b * DP.Nc + c) * IMG, X, ln);
     sm_store(S0, X, ln);  // S0 = Carry through the three conjugations
-    auto conj_by_carry = [&](const double *img, HM &out) {
-        img_load(img, X, ln);
-        __syncthreads();
-        sm_store(S1, X, ln);
-        __syncthreads();
-        hm_zero(X);
-        mm<false, false, false, false>(S0, S1, X, ln);  // Carry Y
-        __syncthreads();
-        sm_store(S1, X, ln);
-        __syncthreads();
-        hm_zero(out);
-        mm<false, false, true, true>(S1, S0, out, ln);  // (Carry Y) Carry^dag
-    };
-    conj_by_carry(B.Me + be * IMG, Mp);
+    conj_by_carry<true>(B.Me + be * IMG, S0, S1, X, Mp, ln);
     img_store(B.Mp + bec * IMG, Mp, ln);
-    conj_by_carry(B.Sx + bec * IMG, Tc);
-    conj_by_carry(B.Tot + be * IMG, Tt);
+    conj_by_carry<true>(B.Sx + bec * IMG, S0, S1, X, Tc, ln);
+    conj_by_carry<true>(B.Tot + be * IMG, S0, S1, X, Tt, ln);
     __syncthreads();
     sm_store(S0, Tc, ln);
     sm_store(S1, Mp, ln);
@@ -744,7 +655,7 @@ __global__ __launch_bounds__(NTHREADS, 1) void k_derr_grad(DenseProblem DP, Dens
             const double tr = wg_sum(acc, lds, ln);
             if (threadIdx.x == 0) {
                 if (u < P.np) out[(size_t)k * P.np + u] = tr;
-                else B.Fd2add[(be * P.Nt + k) * DP.nva + (u - P.np)] = tr;  // step k's x_add term (k_dadd_err)
+                else B.Fd2add[(be * P.Nt + k) * DP.nva + (u - P.np)] = tr;  // step k's x_add term (k_dadd)
             }
         }
         hm_zero(Bp);
@@ -758,13 +669,13 @@ constexpr size_t kLds = (size_t)LDS_TOTAL * sizeof(double);
 }  // namespace
 
 hipError_t set_lds_limits() {
-    const void *fs[] = {reinterpret_cast<const void *>(&k_dexp),      reinterpret_cast<const void *>(&k_dexp_raw),
-                        reinterpret_cast<const void *>(&k_dscan),     reinterpret_cast<const void *>(&k_dcarry),
-                        reinterpret_cast<const void *>(&k_dmc),       reinterpret_cast<const void *>(&k_dgrad),
-                        reinterpret_cast<const void *>(&k_dlocal),    reinterpret_cast<const void *>(&k_dwsum),
-                        reinterpret_cast<const void *>(&k_derr_scan), reinterpret_cast<const void *>(&k_dmce),
-                        reinterpret_cast<const void *>(&k_derr_grad), reinterpret_cast<const void *>(&k_dexp_piv),
-                        reinterpret_cast<const void *>(&k_dexp_raw_piv)};
+    const void *fs[] = {reinterpret_cast<const void *>(&k_dexp<false>),     reinterpret_cast<const void *>(&k_dexp<true>),
+                        reinterpret_cast<const void *>(&k_dexp_raw<false>), reinterpret_cast<const void *>(&k_dexp_raw<true>),
+                        reinterpret_cast<const void *>(&k_dscan),           reinterpret_cast<const void *>(&k_dcarry),
+                        reinterpret_cast<const void *>(&k_dmc),             reinterpret_cast<const void *>(&k_dgrad),
+                        reinterpret_cast<const void *>(&k_dlocal),          reinterpret_cast<const void *>(&k_dwsum),
+                        reinterpret_cast<const void *>(&k_derr_scan),       reinterpret_cast<const void *>(&k_dmce),
+                        reinterpret_cast<const void *>(&k_derr_grad)};
     for (const void *f : fs) {
         hipError_t e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLds);
         if (e != hipSuccess) return e;
@@ -795,18 +706,15 @@ __global__ __launch_bounds__(256) void k_img_rows(const double *img, grape::cd *
     const double *src = img + (size_t)blockIdx.x * IMG;
     grape::cd *dst = rows + (size_t)blockIdx.x * D * D;
     for (int t = threadIdx.x; t < D * D; t += blockDim.x) {
-        const int row = t / D, col = t % D;
-        const int w = col >> 4, tr = row >> 4, r = (row & 15) >> 2, l = ((row & 3) << 4) | (col & 15);
-        const size_t o = (size_t)((w * 4 + tr) * 4 + r) * 64 + l;
-        dst[t] = grape::cmake(src[o], src[IMG / 2 + o]);
+        const int o = img_offset(t / D, t % D);
+        dst[t] = grape::cmake(src[o], src[PLANE + o]);
     }
 }
 
 hipError_t launch_variant_table(const DenseProblem &P, const DenseBatch &B, grape::cd *rows, hipStream_t st,
                                 bool pivot) {
     const unsigned n = (unsigned)((long)B.nb * P.P.Nt * P.P.nv);
-    if (pivot) hipLaunchKernelGGL(k_dexp_piv, dim3(n), dim3(NTHREADS), kLds, st, P, B);
-    else hipLaunchKernelGGL(k_dexp, dim3(n), dim3(NTHREADS), kLds, st, P, B);
+    hipLaunchKernelGGL(pivot ? k_dexp<true> : k_dexp<false>, dim3(n), dim3(NTHREADS), kLds, st, P, B);
     hipLaunchKernelGGL(k_img_rows, dim3(n), dim3(256), 0, st, B.E, rows, P.P.D);
     return hipGetLastError();
 }
@@ -815,7 +723,7 @@ hipError_t launch_pipeline(const DenseProblem &P, const DenseBatch &B, hipStream
     const unsigned nsteps = (unsigned)((long)B.nb * P.P.Nt);
     const unsigned nchunks = (unsigned)((long)B.nb * P.Nc);
     mark(GRAPE_KERNEL_DEXP, 0);
-    hipLaunchKernelGGL(k_dexp, dim3(nsteps * (unsigned)P.P.nv), dim3(NTHREADS), kLds, st, P, B);
+    hipLaunchKernelGGL(k_dexp<false>, dim3(nsteps * (unsigned)P.P.nv), dim3(NTHREADS), kLds, st, P, B);
     mark(GRAPE_KERNEL_DEXP, 1);
     mark(GRAPE_KERNEL_DSCAN, 0);
     hipLaunchKernelGGL(k_dscan, dim3(nchunks), dim3(NTHREADS), kLds, st, P, B);
@@ -833,14 +741,14 @@ hipError_t launch_pipeline(const DenseProblem &P, const DenseBatch &B, hipStream
     if (P.P.ne == 0) {
         mark(GRAPE_KERNEL_DGRAD, 0);
         hipLaunchKernelGGL(k_dgrad, dim3(nsteps), dim3(NTHREADS), kLds, st, P, B);
-        if (P.nva > 0) hipLaunchKernelGGL(k_dadd, dim3((unsigned)(B.nb * P.nva)), dim3(256), 0, st, P, B);
+        if (P.nva > 0) hipLaunchKernelGGL(k_dadd, dim3((unsigned)(B.nb * P.nva)), dim3(256), 0, st, P, B.Fadd, B.Fdx);
         mark(GRAPE_KERNEL_DGRAD, 1);
         return hipGetLastError();
     }
     const unsigned nerr_chunks = nchunks * (unsigned)P.P.ne;
     mark(GRAPE_KERNEL_GRAD, 0);
     hipLaunchKernelGGL(k_dlocal, dim3(nsteps * (unsigned)P.nz), dim3(NTHREADS), kLds, st, P, B);
-    if (P.nva > 0) hipLaunchKernelGGL(k_dadd, dim3((unsigned)(B.nb * P.nva)), dim3(256), 0, st, P, B);
+    if (P.nva > 0) hipLaunchKernelGGL(k_dadd, dim3((unsigned)(B.nb * P.nva)), dim3(256), 0, st, P, B.Fadd, B.Fdx);
     mark(GRAPE_KERNEL_GRAD, 1);
     mark(GRAPE_KERNEL_ERR_SCAN, 0);
     hipLaunchKernelGGL(k_dwsum, dim3(nerr_chunks), dim3(NTHREADS), kLds, st, P, B);
@@ -854,7 +762,7 @@ hipError_t launch_pipeline(const DenseProblem &P, const DenseBatch &B, hipStream
     mark(GRAPE_KERNEL_ERR_GRAD, 0);
     hipLaunchKernelGGL(k_derr_grad, dim3(nerr_chunks), dim3(NTHREADS), kLds, st, P, B);
     if (P.nva > 0)
-        hipLaunchKernelGGL(k_dadd_err, dim3((unsigned)(B.nb * P.P.ne * P.nva)), dim3(256), 0, st, P, B);
+        hipLaunchKernelGGL(k_dadd, dim3((unsigned)(B.nb * P.P.ne * P.nva)), dim3(256), 0, st, P, B.Fd2add, B.Fd2dx);
     mark(GRAPE_KERNEL_ERR_GRAD, 1);
     return hipGetLastError();
 }
@@ -862,26 +770,29 @@ hipError_t launch_pipeline(const DenseProblem &P, const DenseBatch &B, hipStream
 // padded image <-> column-major d x d complex (the C ABI's layout), one workgroup per matrix
 __global__ __launch_bounds__(256) void k_img_cols(const double *img, grape::cd *cols, int D) {
     for (int t = threadIdx.x; t < D * D; t += blockDim.x) {
-        const int col = t / D, row = t % D;
-        const int w = col >> 4, tr = row >> 4, r = (row & 15) >> 2, l = ((row & 3) << 4) | (col & 15);
-        const size_t o = (size_t)((w * 4 + tr) * 4 + r) * 64 + l;
-        cols[t] = grape::cmake(img[o], img[IMG / 2 + o]);
+        const int o = img_offset(t % D, t / D);
+        cols[t] = grape::cmake(img[o], img[PLANE + o]);
+    }
+}
+// f of every element of the zero-padded matrix into the image
+template <class F>
+__device__ __forceinline__ void cols_to_img(const grape::cd *cols, double *img, int D, const F &f) {
+    for (int o = threadIdx.x; o < PLANE; o += blockDim.x) {
+        int row, col;
+        img_rowcol(o, row, col);
+        const bool in = row < D && col < D;
+        const grape::cd v = f(in ? cols[(size_t)row + (size_t)col * D] : grape::cmake(0.0, 0.0));
+        img[o] = v.re;
+        img[PLANE + o] = v.im;
     }
 }
 __global__ __launch_bounds__(256) void k_cols_img(const grape::cd *cols, double *img, int D) {
-    for (int o = threadIdx.x; o < 64 * 64; o += blockDim.x) {
-        const int l = o & 63, r = (o >> 6) & 3, t = (o >> 8) & 3, w = o >> 10;
-        const int row = 16 * t + (l >> 4) + 4 * r, col = 16 * w + (l & 15);
-        const bool in = row < D && col < D;
-        const grape::cd v = in ? cols[(size_t)row + (size_t)col * D] : grape::cmake(0.0, 0.0);
-        img[o] = v.re;
-        img[IMG / 2 + o] = v.im;
-    }
+    cols_to_img(cols, img, D, [](grape::cd v) { return v; });
 }
 
 hipError_t launch_slice_forward(const DenseProblem &P, const DenseBatch &B, grape::cd *Ucols, hipStream_t st) {
     if (B.nb != 1 || !B.Ub) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(k_dexp, dim3((unsigned)P.P.Nt * (unsigned)P.P.nv), dim3(NTHREADS), kLds, st, P, B);
+    hipLaunchKernelGGL(k_dexp<false>, dim3((unsigned)P.P.Nt * (unsigned)P.P.nv), dim3(NTHREADS), kLds, st, P, B);
     hipLaunchKernelGGL(k_dscan, dim3((unsigned)P.Nc), dim3(NTHREADS), kLds, st, P, B);
     hipLaunchKernelGGL(k_dcarry, dim3(1), dim3(NTHREADS), kLds, st, P, B);  // carries and U (F, M unused)
     hipLaunchKernelGGL(k_img_cols, dim3(1), dim3(256), 0, st, B.Ub, Ucols, P.P.D);
@@ -898,33 +809,24 @@ hipError_t launch_slice_gradient(const DenseProblem &P, const DenseBatch &B, con
 
 // A = -i dt H of host-tabulated H (closure fallback, column-major d x d), zero-padded images
 __global__ __launch_bounds__(256) void k_tab_images(const grape::cd *H, double *img, int D, double dt) {
-    const grape::cd *src = H + (size_t)blockIdx.x * D * D;
-    double *dst = img + (size_t)blockIdx.x * IMG;
-    for (int o = threadIdx.x; o < 64 * 64; o += blockDim.x) {
-        const int l = o & 63, r = (o >> 6) & 3, t = (o >> 8) & 3, w = o >> 10;
-        const int row = 16 * t + (l >> 4) + 4 * r, col = 16 * w + (l & 15);
-        const bool in = row < D && col < D;
-        const grape::cd h = in ? src[(size_t)row + (size_t)col * D] : grape::cmake(0.0, 0.0);
-        dst[o] = dt * h.im;             // -i dt (re + i im) = dt im - i dt re
-        dst[IMG / 2 + o] = -(dt * h.re);
-    }
+    cols_to_img(H + (size_t)blockIdx.x * D * D, img + (size_t)blockIdx.x * IMG, D,
+                [dt](grape::cd h) { return grape::cmake(dt * h.im, -(dt * h.re)); });  // -i dt (re + i im)
 }
 
 hipError_t launch_table_variants(const grape::cd *H, int D, int n, double dt, double *Aimg, double *Eimg,
                                  grape::cd *rows, int *status, hipStream_t st, bool pivot) {
     if (n <= 0) return hipSuccess;
     hipLaunchKernelGGL(k_tab_images, dim3((unsigned)n), dim3(256), 0, st, H, Aimg, D, dt);
-    if (pivot)
-        hipLaunchKernelGGL(k_dexp_raw_piv, dim3((unsigned)n), dim3(NTHREADS), kLds, st, Aimg, Eimg, status, nullptr);
-    else hipLaunchKernelGGL(k_dexp_raw, dim3((unsigned)n), dim3(NTHREADS), kLds, st, Aimg, Eimg, status, nullptr);
+    hipLaunchKernelGGL(pivot ? k_dexp_raw<true> : k_dexp_raw<false>, dim3((unsigned)n), dim3(NTHREADS), kLds, st, Aimg,
+                       Eimg, status, nullptr);
     hipLaunchKernelGGL(k_img_rows, dim3((unsigned)n), dim3(256), 0, st, Eimg, rows, D);
     return hipGetLastError();
 }
 
 hipError_t launch_expm_raw(const double *A, double *E, int n, int *status, int *mstats, hipStream_t st, bool pivot) {
     if (n <= 0) return hipSuccess;
-    if (pivot) hipLaunchKernelGGL(k_dexp_raw_piv, dim3((unsigned)n), dim3(NTHREADS), kLds, st, A, E, status, mstats);
-    else hipLaunchKernelGGL(k_dexp_raw, dim3((unsigned)n), dim3(NTHREADS), kLds, st, A, E, status, mstats);
+    hipLaunchKernelGGL(pivot ? k_dexp_raw<true> : k_dexp_raw<false>, dim3((unsigned)n), dim3(NTHREADS), kLds, st, A, E,
+                       status, mstats);
     return hipGetLastError();
 }
 

@@ -197,6 +197,18 @@ __device__ __forceinline__ void img_store(double *img, const HM &M, const Lane &
         }
 }
 
+// where element (row, col) lies in a plane of an image (Lane::img of the lane and register that hold it),
+// and the element at offset o
+__device__ __forceinline__ int img_offset(int row, int col) {
+    const int w = col >> 4, tr = row >> 4, r = (row & 15) >> 2, l = ((row & 3) << 4) | (col & 15);
+    return ((w * NT + tr) * 4 + r) * 64 + l;
+}
+__device__ __forceinline__ void img_rowcol(int o, int &row, int &col) {
+    const int l = o & 63, r = (o >> 6) & 3, t = (o >> 8) & 3, w = o >> 10;
+    row = 16 * t + (l >> 4) + 4 * r;
+    col = 16 * w + (l & 15);
+}
+
 // a copy of the lane descriptor whose lane id the compiler cannot see through:
 // index math derived from it is recomputed where used instead of being hoisted
 // out of every enclosing loop and kept live

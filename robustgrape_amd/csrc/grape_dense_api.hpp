@@ -45,7 +45,7 @@ struct DenseBatch {
     double *Fd2;      // [nb][ne]
     double *Fd2dx;    // [nb][ne][nx]
     double *Fd2add;   // [nb][ne][Nt][nva]  H0 / Herror read x_add: step k's term of F_d2err_dx_add[q] (k_derr_grad;
-                      //                    k_dadd_err sums them onto the target's part)
+                      //                    k_dadd sums them onto the target's part)
     grape::cd *gp_scr;  // general projector: head scratch (grape_projector_api.hpp)
 };
 
@@ -54,14 +54,14 @@ constexpr int kImgDoubles = 2 * 64 * 64;
 // Pipeline of one batch (k_dexp, k_dscan, k_dcarry, k_dmc, k_dgrad) on `st`.
 hipError_t launch_pipeline(const DenseProblem &P, const DenseBatch &B, hipStream_t st,
                            const grape_host::KMark &mark);
-// n exponentials of padded images (grape_expm_batch for 12 < d <= 64).  pivot: k_dexp_raw_piv, the
+// n exponentials of padded images (grape_expm_batch for 12 < d <= 64).  pivot: k_dexp_raw<true>, the
 // pivoted Pade solve for a general A (grape_expm_batch_general); false needs a skew-Hermitian A.
 hipError_t launch_expm_raw(const double *A, double *E, int n, int *status, int *mstats, hipStream_t st,
                            bool pivot = false);
 hipError_t set_lds_limits();
 // Every variant P.vs[0..P.nv) of every step of ONE evaluation (B.nb = 1): k_dexp into the
 // images B.E, then converted to row-major d x d tiles rows[Nt][nv][D][D] (the table the
-// materialised-derivative kernels of grape_unitary.hip read).  pivot: k_dexp_piv (general H0 / Herror).
+// materialised-derivative kernels of grape_unitary.hip read).  pivot: k_dexp<true> (general H0 / Herror).
 hipError_t launch_variant_table(const DenseProblem &P, const DenseBatch &B, grape::cd *rows, hipStream_t st,
                                 bool pivot = false);
 // Time sharding: one evaluation (B.nb = 1) of a slice plan.  Forward: the slice's
@@ -73,7 +73,7 @@ hipError_t launch_slice_gradient(const DenseProblem &P, const DenseBatch &B, con
 // Closure fallback above GRAPE_MAX_SMALL_DIM: n host-tabulated H (column-major d x d) -> exp(-i dt H)
 // as row-major d x d tiles (`rows`), through the padded images Aimg / Eimg (n images each); the
 // no-interchange solve needs a Hermitian H (checked on the host, robustgrape_amd/engine.py); pivot:
-// k_dexp_raw_piv, any H (plans created with GRAPE_OPT_GENERAL_H0)
+// k_dexp_raw<true>, any H (plans created with GRAPE_OPT_GENERAL_H0)
 hipError_t launch_table_variants(const grape::cd *H, int D, int n, double dt, double *Aimg, double *Eimg,
                                  grape::cd *rows, int *status, hipStream_t st, bool pivot = false);
 

@@ -202,7 +202,7 @@ struct grape_plan {
     // (grape_unitary.hip k_u_fid_head / k_u_fid_contract), one evaluation at a time
     bool general_h0 = false;
     // 12 < d <= 64 created with GRAPE_OPT_GENERAL_H0: every exponential through the dense engine's
-    // pivoted kernels (k_dexp_piv / k_dexp_raw_piv), valid for any generator
+    // pivoted kernels (k_dexp<true> / k_dexp_raw<true>), valid for any generator
     bool pivot = false;
     cd *ud_Ci = nullptr, *d_G = nullptr;
     cd *d_fscr = nullptr;        // d > 12: the fidelity head's tiles (global scratch)

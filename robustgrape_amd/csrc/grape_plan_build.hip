@@ -157,7 +157,7 @@ int create_dense(const grape_desc *desc, grape_plan *p, bool xadd_dep, const Pro
     // H0 (or Herror) reading x_add: without error sources k_dgrad adds each step's x_add variant (DP.nva);
     // with error sources (round 6) the variant table carries the x_add variants too (the small engine's
     // layout: nvg = np + na gradient parameters per step), k_dlocal / k_derr_grad write their per-step x_add
-    // terms and k_dadd / k_dadd_err sum them onto the target's parts (UnitaryCalculations.jl:57-64, 87-95)
+    // terms and k_dadd sums them onto the target's parts (UnitaryCalculations.jl:57-64, 87-95)
     // Hermitian H0: checked for every engine in choose_route (the dense no-interchange
     // solve relies on it too, grape_dense.hpp).  The error variants exponentiate
     // H0 + err Herror (err <= eps2): Hermitian error terms keep them inside that proof.
@@ -862,7 +862,7 @@ static int setup_sectors(PlanBuild &b) {
 }
 
 // 12 < d <= 64 with GRAPE_OPT_GENERAL_H0, operator basis: the operator images and the problem
-// ud_propagators_dev's dense branch exponentiates from (k_dexp_piv over the variant list): the terms,
+// ud_propagators_dev's dense branch exponentiates from (k_dexp<true> over the variant list): the terms,
 // scalars and x layout are the general path's
 static int setup_pivot_dense(PlanBuild &b) {
     if (!b.rt.pivot || b.rt.tables) return GRAPE_OK;

@@ -16,6 +16,8 @@
 // With error sources (GRAPE_OPT_TILED_ERR; launch_err below): the variants of every step through k_tgen and the
 // same exponential, k_tstencil, the local-frame images through k_tprod (ErrAddr), then k_twsum, k_tprefix,
 // k_terrhead1/2, the conjugations by the carries and the walk B_{k+1} = B_k + W_k M' - M' W_k with k_terrcontract.
+// One body each for what the two paths share: launch_variant_exp (k_tgen, then the exponential's launches) and
+// target_rows (the x_add rows of k_thead1 and k_terrhead1).
 #include "grape_tiled.hpp"
 #include "grape_tiled_api.hpp"
 
@@ -200,22 +202,21 @@ __device__ __forceinline__ int stage_coefs(const grape::DevProblem &P, const dou
                                            const grape::VSpec &vs, double *gre, double *gim, int *gop) {
     const double *xk = xb + (size_t)k * P.np;
     const double *xadd = xb + (size_t)P.np * P.Nt;
+    auto put = [&](int t, int op, cd c) {  // -i dt c into slot t
+        gre[t] = P.dt * c.im;
+        gim[t] = -(P.dt * c.re);
+        gop[t] = op;
+    };
     for (int t = threadIdx.x; t < P.n_h0; t += blockDim.x) {
         const Term tm = P.h0[t];
-        const cd c = grape::term_coef(tm, k + 1, xk, xadd, vs.pert);
-        gre[t] = P.dt * c.im;  // -i dt c
-        gim[t] = -(P.dt * c.re);
-        gop[t] = tm.op;
+        put(t, tm.op, grape::term_coef(tm, k + 1, xk, xadd, vs.pert));
     }
     int n = P.n_h0;
     if (vs.err >= 0) {
         const int t0 = P.err_off[vs.err], ne = P.err_off[vs.err + 1] - t0;
         for (int t = threadIdx.x; t < ne; t += blockDim.x) {
             const Term tm = P.err[t0 + t];
-            const cd c = grape::cscale(vs.errval, grape::term_coef(tm, k + 1, xk, xadd, vs.pert));
-            gre[n + t] = P.dt * c.im;
-            gim[n + t] = -(P.dt * c.re);
-            gop[n + t] = tm.op;
+            put(n + t, tm.op, grape::cscale(vs.errval, grape::term_coef(tm, k + 1, xk, xadd, vs.pert)));
         }
         n += ne;
     }
@@ -330,6 +331,14 @@ void launch_exp_steps(const Geo &g, const ExpSlab &X, const int *ctl, int n, dou
     for (int s = 0; s < 4 + smax; ++s) launch_prod<false, false>(g, ExpStep{s, ctl, X, out, img}, n, st);
 }
 
+// variant vs of the n steps from s0 of the pass (raw: the images s0 ...): A / 2^s, then its exponential into out
+void launch_variant_exp(const TiledProblem &TP, const Geo &g, const double *x, const double *raw, int s0, int n,
+                        const grape::VSpec &vs, const int *ctl, const ExpSlab &X, double *out, int smax,
+                        hipStream_t st) {
+    hipLaunchKernelGGL(k_tgen, dim3((unsigned)n), dim3(NTHREADS), 0, st, TP, x, raw, s0, vs, ctl, X.A);
+    launch_exp_steps(g, X, ctl + s0, n, out, smax, st);
+}
+
 // ---------------------------------------------------------------------------
 // head
 // ---------------------------------------------------------------------------
@@ -373,6 +382,31 @@ __global__ __launch_bounds__(NTHREADS) void k_ttarget(TiledProblem TP, const dou
     }
 }
 
+// The target rows of a head: out[q] = (scale (2 sum_ij W_i P_j Re(conj(K_ij) Kd_ij) + 2 Re(conj(tau) tr(W Kd)))) / DD
+// for the na images Kd_q that follow K = Kv[0].  K = U0^dag U, scale 1: F_dx_add's target part
+// (FidelityCalculations.jl:67-76); K = Ke, tau = tau_e, scale 2: F_d2err_dx_add's (:96-113)
+__device__ __forceinline__ void target_rows(const TiledProblem &TP, const double *Kv, double tau_re, double tau_im,
+                                            double scale, double *out, double *red) {
+    const grape::DevProblem &P = TP.P;
+    const int Pd = TP.Pd;
+    const size_t plane = (size_t)Pd * Pd, img = 2 * plane;
+    for (int q = 0; q < P.na; ++q) {
+        const double *Kd = Kv + (size_t)(1 + q) * img;
+        double pr = 0.0, dre = 0.0, dim = 0.0;
+        for (size_t a = threadIdx.x; a < plane; a += NTHREADS) {
+            const int row = (int)(a / Pd), col = (int)(a % Pd);
+            const double wr = TP.W[row], pcol = TP.W[col] != 0.0 ? 1.0 : 0.0;
+            pr += wr * (pcol * (Kd[a] * Kv[a] + Kd[plane + a] * Kv[plane + a]));
+            if (row == col) {
+                dre += wr * Kd[a];
+                dim += wr * Kd[plane + a];
+            }
+        }
+        const double s1 = wg_sum(pr, red), tr_re = wg_sum(dre, red), tr_im = wg_sum(dim, red);
+        if (threadIdx.x == 0) out[q] = (scale * (2.0 * s1 + 2.0 * (tau_re * tr_re + tau_im * tr_im))) / P.DD;
+    }
+}
+
 // per evaluation: tau = tr(W K), F, W K, and the target part of F_dx_add     FidelityCalculations.jl:47-54, 67-76
 __global__ __launch_bounds__(NTHREADS) void k_thead1(TiledProblem TP, TiledBatch B) {
     __shared__ double red[NTHREADS];
@@ -401,23 +435,7 @@ __global__ __launch_bounds__(NTHREADS) void k_thead1(TiledProblem TP, TiledBatch
         B.tau[2 * b] = tau_re;
         B.tau[2 * b + 1] = tau_im;
     }
-    for (int q = 0; q < P.na; ++q) {
-        const double *Kd = K + (size_t)(1 + q) * img;
-        double pr = 0.0, dre = 0.0, dim = 0.0;
-        for (size_t a = threadIdx.x; a < plane; a += NTHREADS) {
-            const int row = (int)(a / Pd), col = (int)(a % Pd);
-            const double wr = TP.W[row], pcol = TP.W[col] != 0.0 ? 1.0 : 0.0;
-            pr += wr * (pcol * (Kd[a] * K[a] + Kd[plane + a] * K[plane + a]));
-            if (row == col) {
-                dre += wr * Kd[a];
-                dim += wr * Kd[plane + a];
-            }
-        }
-        const double s1 = wg_sum(pr, red), tr_re = wg_sum(dre, red), tr_im = wg_sum(dim, red);
-        if (threadIdx.x == 0)
-            B.Fdx[(size_t)b * P.nx + (size_t)P.np * P.Nt + q] =
-                (2.0 * s1 + 2.0 * (tau_re * tr_re + tau_im * tr_im)) / P.DD;
-    }
+    target_rows(TP, K, tau_re, tau_im, 1.0, B.Fdx + (size_t)b * P.nx + (size_t)P.np * P.Nt, red);
 }
 
 // M = (2 / DD) (P K^dag W K + conj(tau) W K), T = K^dag (W K)
@@ -732,23 +750,7 @@ __global__ __launch_bounds__(NTHREADS) void k_terrhead1(TiledProblem TP, TiledBa
         B.taue[2 * be] = te_re;
         B.taue[2 * be + 1] = te_im;
     }
-    for (int q = 0; q < P.na; ++q) {
-        const double *Kd = Ke + (size_t)(1 + q) * img;
-        double pr = 0.0, dre = 0.0, dim = 0.0;
-        for (size_t a = threadIdx.x; a < plane; a += NTHREADS) {
-            const int row = (int)(a / Pd), col = (int)(a % Pd);
-            const double wr = TP.W[row], pcol = TP.W[col] != 0.0 ? 1.0 : 0.0;
-            pr += wr * (pcol * (Kd[a] * Ke[a] + Kd[plane + a] * Ke[plane + a]));
-            if (row == col) {
-                dre += wr * Kd[a];
-                dim += wr * Kd[plane + a];
-            }
-        }
-        const double s1 = wg_sum(pr, red), tr_re = wg_sum(dre, red), tr_im = wg_sum(dim, red);
-        if (threadIdx.x == 0)
-            B.Fd2dx[(size_t)be * P.nx + (size_t)P.np * P.Nt + q] =
-                2.0 * (2.0 * s1 + 2.0 * (te_re * tr_re + te_im * tr_im)) / P.DD;
-    }
+    target_rows(TP, Ke, te_re, te_im, 2.0, B.Fd2dx + (size_t)be * P.nx + (size_t)P.np * P.Nt, red);
 }
 
 // M_e = (4 / DD) [P Ke^dag W K + conj(tau_e) W K - (1 + D) W Ue^dag U]
@@ -829,10 +831,7 @@ hipError_t launch_err(const TiledProblem &TP, const TiledBatch &B, const Geo &g,
     for (int s0 = 0; s0 < nsteps; s0 += slab) {
         const int n = std::min(slab, nsteps - s0);
         auto variant = [&](int var, int index, double delta, int err, double errval, double *out) {
-            const grape::VSpec vs = {{var, index, delta}, err, errval};
-            hipLaunchKernelGGL(k_tgen, dim3((unsigned)n), dim3(NTHREADS), 0, st, TP, B.x, (const double *)nullptr, s0, vs,
-                               B.ctl, B.X.A);
-            launch_exp_steps(g, B.X, B.ctl + s0, n, out, smax, st);
+            launch_variant_exp(TP, g, B.x, nullptr, s0, n, {{var, index, delta}, err, errval}, B.ctl, B.X, out, smax, st);
         };
         auto local = [&](int u, int slot) {  // the stencil of B.Ev into slot
             hipLaunchKernelGGL(k_tstencil, dim3((unsigned)n), dim3(NTHREADS), 0, st, TP, B, s0, u);
@@ -907,9 +906,7 @@ hipError_t launch_pipeline(const TiledProblem &TP, const TiledBatch &B, hipStrea
     mark(GRAPE_KERNEL_DEXP, 0);
     for (int s0 = 0; s0 < nsteps; s0 += slab) {
         const int n = std::min(slab, nsteps - s0);
-        hipLaunchKernelGGL(k_tgen, dim3((unsigned)n), dim3(NTHREADS), 0, st, TP, B.x, (const double *)nullptr, s0,
-                           kNominal, B.ctl, B.X.A);
-        launch_exp_steps(g, B.X, B.ctl + s0, n, B.E + (size_t)s0 * img, smax, st);
+        launch_variant_exp(TP, g, B.x, nullptr, s0, n, kNominal, B.ctl, B.X, B.E + (size_t)s0 * img, smax, st);
     }
     mark(GRAPE_KERNEL_DEXP, 1);
     mark(GRAPE_KERNEL_DSCAN, 0);
@@ -938,10 +935,7 @@ hipError_t launch_pipeline(const TiledProblem &TP, const TiledBatch &B, hipStrea
         launch_prod<false, false>(g, PipeAddr{c, ST_Y1, s0}, n, st);
         launch_prod<false, true>(g, PipeAddr{c, ST_Y2, s0}, n, st);
         for (int p = 0; p < P.np; ++p) {
-            const grape::VSpec pp = {{grape::VAR_X, p, P.eps}, -1, 0.0};
-            hipLaunchKernelGGL(k_tgen, dim3((unsigned)n), dim3(NTHREADS), 0, st, TP, B.x, (const double *)nullptr,
-                               s0, pp, B.ctl, B.X.A);
-            launch_exp_steps(g, B.X, B.ctl + s0, n, B.Ev, smax, st);
+            launch_variant_exp(TP, g, B.x, nullptr, s0, n, {{grape::VAR_X, p, P.eps}, -1, 0.0}, B.ctl, B.X, B.Ev, smax, st);
             hipLaunchKernelGGL(k_tcontract, dim3((unsigned)n), dim3(NTHREADS), 0, st, TP, B, s0, p);
         }
     }
@@ -964,9 +958,7 @@ hipError_t launch_expm_raw(int d, const double *A, double *E, int n, const ExpSl
     if (e != hipSuccess) return e;
     for (int s0 = 0; s0 < n; s0 += X.slab) {
         const int m = std::min(X.slab, n - s0);
-        hipLaunchKernelGGL(k_tgen, dim3((unsigned)m), dim3(NTHREADS), 0, st, TP, (const double *)nullptr, A, s0,
-                           kNominal, ctl, X.A);
-        launch_exp_steps(g, X, ctl + s0, m, E + (size_t)s0 * img, sm, st);
+        launch_variant_exp(TP, g, nullptr, A, s0, m, kNominal, ctl, X, E + (size_t)s0 * img, sm, st);
     }
     return hipGetLastError();
 }

@@ -375,7 +375,7 @@ def _xadd_err_problem(d, ntimes, nerr=2):
 @pytest.mark.parametrize("d,ntimes,nerr", [(13, 1, 1), (16, 6, 2), (40, 5, 2), (64, 3, 1)])
 def test_dense_xadd_dependent_h0_with_error_sources_match_live_oracle(d, ntimes, nerr):
     """x_add-dependent H0 and Herror with error sources above 12 levels (round 6): the x_add variants in the
-    dense error path (k_dlocal / k_derr_grad over np + na gradient parameters, k_dadd / k_dadd_err) against
+    dense error path (k_dlocal / k_derr_grad over np + na gradient parameters, k_dadd on F_dx_add and on F_d2err_dx_add) against
     the oracle: F, F_dx (incl. F_dx_add), F_d2err, F_d2err_dx (incl. its x_add rows)."""
     from oracle import grape_oracle as O
     from robustgrape_amd import calculate_fidelity_and_derivatives

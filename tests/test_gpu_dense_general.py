@@ -1,5 +1,5 @@
 """Non-Hermitian generators at 13..64 levels: the dense engine's pivoted exponential
-(grape_dense.hpp gj_solve_pivot, k_dexp_piv / k_dexp_raw_piv) and the general path over it
+(grape_dense.hpp gj_solve_pivot, k_dexp<true> / k_dexp_raw<true>) and the general path over it
 (GRAPE_OPT_GENERAL_H0 above 12 levels), against the CPU oracle.
 
 Tolerances:
