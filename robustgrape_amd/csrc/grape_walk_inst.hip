@@ -232,3 +232,14 @@ template hipError_t launch<3>(int, const grape::DevProblem &, const grape::DevBa
 template hipError_t launch<4>(int, const grape::DevProblem &, const grape::DevBatch &, hipStream_t);
 
 }  // namespace grape_walk
+
+#ifdef GRAPE_WIDE_STAMPS
+// the diagnostic build's read-out of the wide walks' stamps (grape_walk_merged.hpp WideStamp), zeroing them after
+extern "C" int grape_diag_wide_stamps(void *dst, size_t bytes) {
+    if (bytes != sizeof(grape::g_wide_stamps)) return -1;
+    if (hipMemcpyFromSymbol(dst, HIP_SYMBOL(grape::g_wide_stamps), bytes) != hipSuccess) return -2;
+    void *p = nullptr;
+    if (hipGetSymbolAddress(&p, HIP_SYMBOL(grape::g_wide_stamps)) != hipSuccess) return -3;
+    return hipMemset(p, 0, bytes) == hipSuccess ? 0 : -4;
+}
+#endif

@@ -191,8 +191,11 @@ __device__ __forceinline__ void wide_store_psi(cd *u, size_t nbe, const cd (&psi
 // sixteen lanes read one row's 128-byte piece per instruction, so every line of x is fetched once and used
 // whole.  (A lane streaming its own row touches one line per lane and step and finds it evicted eight steps
 // later at 262 144 lanes: the first cut of the wide walks fetched 4.8 GB per forward launch for 1.08 GB of
-// controls.)  The tile is loaded where it is needed: the other workgroups of the SIMD cover the one load latency
-// per kFdxTile steps, and a register copy of the next tile (16 values and their addresses per lane) cost the
+// controls.)  The tile is loaded where it is needed: the load itself is cheap (cutting the tile
+// blocks moved nothing), but a wave spends a sixth to a quarter of its life between the end of a tile's steps and
+// the barrier behind the next load, waiting for its workgroup's other wave, which sits on another SIMD at another
+// place of that SIMD's queue (profiles/r15/attribution.txt; wide_set_prio keeps the waves of a SIMD together),
+// and a register copy of the next tile (16 values and their addresses per lane) cost the
 // gradient walk its fourth wave.  Rows past the last evaluation read the last one's.
 constexpr int kFdxTile = 16;  // steps per tile: the wide walks' x tiles, the merged gradient walks' F_dx flush
 __device__ __forceinline__ void wide_load_x(double (*tile)[kFdxTile + 1], const double *x, int nx, int nbe, int j0, int Nt) {
@@ -234,6 +237,72 @@ __device__ __forceinline__ void wide_flush_full(const double (*tile)[kFdxTile + 
     for (int i = 0; i < kTrips; ++i)
         *reinterpret_cast<double *>(reinterpret_cast<char *>(fb + (size_t)i * kStep * nx) + off) = tile[r0 + i * kStep][j];
 }
+// In-kernel stamps of the wide walks -- a diagnostic build only (-DGRAPE_WIDE_STAMPS=1 through
+// scripts/build_variants.py; scripts/probes/wide_attribution.py reads them): the default build defines nothing of
+// this and WideStamp is empty.  Every wave takes the shader clock (s_memtime) and the constant 100 MHz clock
+// (s_memrealtime) before its first tile and after its last, sums the shader clocks it spent in tile seams (from the
+// end of a tile's steps, or the start, to the barrier behind the next tile's load), and its first lane writes them
+// with where the wave ran (HW_ID, XCC_ID) to a buffer no kernel reads.
+#ifdef GRAPE_WIDE_STAMPS
+constexpr int kWideStampWaves = 8192, kWideStampWords = 8;
+static __device__ unsigned long long g_wide_stamps[2][kWideStampWaves][kWideStampWords];
+struct WideStamp {
+    unsigned long long t0, r0, ts, seam;
+    unsigned nseam;
+    __device__ __forceinline__ void begin() {
+        t0 = ts = __builtin_amdgcn_s_memtime();
+        r0 = __builtin_amdgcn_s_memrealtime();
+        seam = 0;
+        nseam = 0;
+    }
+    __device__ __forceinline__ void seam_in() { ts = __builtin_amdgcn_s_memtime(); }
+    __device__ __forceinline__ void seam_out() {
+        seam += __builtin_amdgcn_s_memtime() - ts;
+        ++nseam;
+    }
+    __device__ __forceinline__ void end(int kernel) {
+        const unsigned long long t1 = __builtin_amdgcn_s_memtime(), r1 = __builtin_amdgcn_s_memrealtime();
+        const unsigned hw = __builtin_amdgcn_s_getreg(4 | (31 << 11)), xcc = __builtin_amdgcn_s_getreg(20 | (31 << 11));
+        const unsigned wave = blockIdx.x * (kWalkBlock / 64) + threadIdx.x / 64;
+        if (threadIdx.x % 64 == 0 && wave < (unsigned)kWideStampWaves) {
+            unsigned long long *o = g_wide_stamps[kernel][wave];
+            o[0] = t0, o[1] = r0, o[2] = t1, o[3] = r1, o[4] = seam, o[5] = ((unsigned long long)xcc << 32) | hw;
+            o[6] = nseam, o[7] = 1;
+        }
+    }
+};
+#else
+struct WideStamp {
+    __device__ __forceinline__ void begin() {}
+    __device__ __forceinline__ void seam_in() {}
+    __device__ __forceinline__ void seam_out() {}
+    __device__ __forceinline__ void end(int) {}
+};
+#endif
+// A wave's issue priority from its own progress.  The four waves of a SIMD start together (one round of workgroups
+// fills the chip at 262 144 lanes) and VALU issue goes by priority, then age: left alone, the oldest wave runs
+// nearly unimpeded and the four finish one after another -- at 0.47, 0.57, 0.82 and 0.94 of the kernel, the last
+// alone for a ninth of it, and even the wave that finishes first issues in under half the cycles of its life
+// (profiles/r15/attribution.txt).  So a wave
+// sets its priority once per tile from the quarter of the walk it is in, 3, 2, 1, 0: a wave that is behind outranks
+// one that is ahead, the spread is held within a quarter of the walk (a wave that crosses into the next quarter
+// yields to every wave still in this one), and only the last quarter drains in age order.  With it the waves
+// finished at 0.81 .. 0.96 (stamps of a tree whose forward walk also had a per-tile guard, since taken out: DESIGN.md
+// 9).  s_setprio is scalar and ignores EXEC: it sits where the whole wave passes once per tile.
+// (Two tiles a level, cyclic, closed the finish times less -- a wave that wraps outranks the ones it left behind --
+// and measured 154 M evaluations/s where this measured 157, both on that tree: DESIGN.md 9.)
+// Measured at the one shape where all waves of a SIMD start together: C2, one round of workgroups.  With more
+// than one round a fresh wave at priority 3 outranks resident waves near their end, which that measurement does not
+// cover; a walk of fewer than four tiles never reaches the last quarter, so the walks put the priority back to 0
+// behind their last tile (wide_reset_prio) and no epilogue runs above it.
+__device__ __forceinline__ void wide_set_prio(int done, int of) {  // done of `of` tiles walked (wave-uniform)
+    const int d4 = 4 * done;  // the quarter is floor(4 done / of), by compares: no scalar division
+    if (d4 < of) __builtin_amdgcn_s_setprio(3);
+    else if (d4 < 2 * of) __builtin_amdgcn_s_setprio(2);
+    else if (d4 < 3 * of) __builtin_amdgcn_s_setprio(1);
+    else __builtin_amdgcn_s_setprio(0);
+}
+__device__ __forceinline__ void wide_reset_prio() { __builtin_amdgcn_s_setprio(0); }
 template <int DA, bool TWB, bool LAD>
 __device__ __forceinline__ void wide_fwd_body(const DevProblem &PA, const DevBatch &BA, const DevProblem &PB,
                                               const DevBatch &BB) {
@@ -276,12 +345,16 @@ __device__ __forceinline__ void wide_fwd_body(const DevProblem &PA, const DevBat
     const bool full = wide_group_full(L.nbe);
     const unsigned off = wide_tile_offset(PA.nx);
     const double *xb = BA.x + (size_t)blockIdx.x * kWalkBlock * PA.nx;  // the workgroup's first row
+    WideStamp stamp;  // (empty but in the diagnostic build)
+    stamp.begin();
 #pragma unroll 1
     for (int j0 = 0; j0 < PA.Nt; j0 += kFdxTile) {
         const int nj = min(kFdxTile, PA.Nt - j0);
+        wide_set_prio(j0 / kFdxTile, (PA.Nt + kFdxTile - 1) / kFdxTile);
         if (full && j0 + kFdxTile <= PA.Nt) wide_load_x_full(xtile, xb + j0, PA.nx, off);
         else wide_load_x(xtile, BA.x, PA.nx, L.nbe, j0, PA.Nt);
         __syncthreads();
+        stamp.seam_out();
         int t = 0;  // (unrolled by hand, as k_walk_fwd_m below)
 #pragma unroll 1
         for (; t + 1 < nj; t += 2) {
@@ -289,8 +362,11 @@ __device__ __forceinline__ void wide_fwd_body(const DevProblem &PA, const DevBat
             step(xtile[threadIdx.x][t + 1]);
         }
         if (t < nj) step(xtile[threadIdx.x][t]);
+        stamp.seam_in();
         __syncthreads();
     }
+    wide_reset_prio();
+    stamp.end(0);
     if constexpr (FRAME) {  // psi_N = D_{N-1} chi_N: the head and the gradient walk read the lab frame
         cd pw[DA];
         ladder_powers<DA>(gauge_cis_tab(PA.gauge_a * xprev, ctab), pw);  // (the last step's phase, once per kernel)
@@ -1026,15 +1102,20 @@ __device__ __forceinline__ void wide_grad_body(const DevProblem &PA, const DevBa
     const bool full = wide_group_full(L.nbe);
     const unsigned off = wide_tile_offset(PA.nx);
     const size_t row0 = (size_t)blockIdx.x * kWalkBlock * PA.nx;  // the workgroup's first row of x and of F_dx
+    WideStamp stamp;  // (empty but in the diagnostic build)
+    stamp.begin();
 #pragma unroll 1
     for (int j0 = jlast; j0 >= 0; j0 -= kFdxTile) {
         const int nj = min(kFdxTile, PA.Nt - j0);
         const bool fast = full && j0 + kFdxTile <= PA.Nt;  // (workgroup-uniform)
+        wide_set_prio((jlast - j0) / kFdxTile, jlast / kFdxTile + 1);
         if (fast) wide_load_x_full(ftile, BA.x + row0 + j0, PA.nx, off);
         else wide_load_x(ftile, BA.x, PA.nx, L.nbe, j0, PA.Nt);
         __syncthreads();
+        stamp.seam_out();
 #pragma unroll 1
         for (int t = nj - 1; t >= 0; --t) ftile[threadIdx.x][t] = step(ftile[threadIdx.x][t]);
+        stamp.seam_in();
         __syncthreads();
         if (fast) {
             wide_flush_full(ftile, BA.Fdx + row0 + j0, PA.nx, off);
@@ -1048,6 +1129,8 @@ __device__ __forceinline__ void wide_grad_body(const DevProblem &PA, const DevBa
         }
         __syncthreads();
     }
+    wide_reset_prio();
+    stamp.end(1);
 }
 template <int DA, bool TWB, bool LAD, bool R1, bool WIDE = false>
 __global__ __launch_bounds__(kWalkBlock, (WIDE ? GRAPE_WALK_WIDE_GRAD_WAVES : R1 ? GRAPE_WALK_R1_WAVES : GRAPE_WALK_MERGED_WAVES)) void k_walk_grad_m(DevProblem PA, DevBatch BA,
